@@ -1,9 +1,15 @@
 #!/usr/bin/env python3
 """bench.py -- pixels/s change-detected on MI355X (BASELINE.json metric), one JSON line.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run does what the headline needs and no more: it sets the tile leg up, runs W warmup
+steps, times K steps, writes the last step's outputs with --dump-outputs, and prints the JSON
+line.  Everything else below (the resident leg and its roofline, the oracle parity sample of the
+tile, the lossless tile run, the other configs' legs, the chip packer, the CPU baselines, the
+north-star run of N > 1) is measured with --full only.
 
 Headline (``value``; SURVEY.md §8(d): P / wall time including H2D and the D2H of the packed
 results; BASELINE.json configs[2], the CONUS ARD tile the metric names): every rank (one process
@@ -16,10 +22,17 @@ on the device and fetched back, per-chip summaries gathered on rank 0.  Chip ARD
 device generator (ccdgpu.synth.TileSource): each batch is generated on the GPU and copied into
 pinned host memory before the runner uploads it, so every chip is distinct and reaches the
 detection path through host memory and PCIe like fetched ARD (its GPU time and device-to-host
-copy are NOT excluded: the headline is pessimistic by that much).  A "step" = 1/K of the tile
-(ceil(2500 / K) chips per rank); the K steps are timed as one changedetection call bracketed by
-a barrier and a device synchronize; W warmup steps run first on chips of another tile.  Weak
-scaling: one tile per GPU (rank r's tile = chips 2500 r .. 2500 r + 2499 of the generator).
+copy are NOT excluded: the headline is pessimistic by that much).  A "step" = ``--step-chips``
+chips per rank (500, a fifth of the tile: the default K = 5 is one full tile, more steps go on
+into the generator's next tiles); the K steps are timed as one changedetection call bracketed by
+a barrier and a device synchronize; W warmup steps of the same size run first on chips of another
+tile range.  Weak scaling: K steps per GPU (all ranks' chips share one dynamic queue).
+
+--dump-outputs DIR: what the timed call handed its sink in the last step -- the device-packed
+rows and processing-mask words of 8 fixed pixels of every chip of that step (of its last 500
+chips), and the per-chip summaries the call returns for them -- as float64 DIR/<name>.npy
+(dump_outputs).  Chips, pixels and inputs are the same from run to run, so two builds can be
+compared array for array.
 
 ``resident``: the detection hot path alone with inputs resident in HBM (64 tile chips per GPU,
 one ragged batch per step, K steps), the kernel behind the ``roofline`` (counted FP64 flops per
@@ -46,6 +59,9 @@ FP64_PEAK_TFLOPS = 78.6   # MI355X FP64 vector (spec)
 HBM_PEAK_GBS = 8000.0     # MI355X HBM3E (spec)
 PIXELS_PER_CHIP = 10000
 TILE_CHIPS = 2500
+DUMP_PIXELS = 8               # --dump-outputs: sampled pixels per chip of the last step ...
+DUMP_CHIPS = 500              # ... of at most this many chips (its last ones): ~30 MB of change-dense C5 rows
+DUMP_MAX_BYTES = 64 << 20     # --dump-outputs: bound on all arrays together
 CONFIG_NAMES = {
     2: 'C2: synthetic 100x100 chips, ~1000 obs x 7 bands + QA',
     3: 'C3: CONUS ARD tile chips (100x100 px, L4-L8 1982-2017 cadence, the tile\'s base-cadence / sidelap mix)',
@@ -59,6 +75,15 @@ def parse():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=5)
     ap.add_argument('--warmup', type=int, default=1)
+    ap.add_argument('--full', action='store_true',
+                    help='also measure and check everything beside the headline: the resident leg and its roofline, '
+                         'the tile\'s oracle parity sample, the lossless tile run, the other configs\' legs, the chip '
+                         'packer, the CPU baselines (and, N > 1, the north-star run)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the timed tile call computed in its last step (sampled rows, mask words, chip '
+                         'summaries) as float64 DIR/<name>.npy')
+    ap.add_argument('--step-chips', type=int, default=TILE_CHIPS // 5,
+                    help='chips per rank of one tile-leg step (default: a fifth of a tile)')
     ap.add_argument('--chips', type=int, default=64, help='chips per GPU per step')
     ap.add_argument('--config', type=int, default=3, choices=sorted(CONFIG_NAMES), help='synthetic config')
     ap.add_argument('--contexts', type=int, default=2,
@@ -69,11 +94,10 @@ def parse():
                     help='pixels of the pyccd-structured restatement baseline sample')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-packer', action='store_true', help='skip the chip-packer (chipmunk decode) leg')
-    ap.add_argument('--tile-chips', type=int, default=TILE_CHIPS, help='chips of the headline tile leg per rank')
     ap.add_argument('--no-resident', action='store_true',
                     help='tile leg only (knob sweeps): no resident leg, roofline null, no CPU baselines')
     ap.add_argument('--no-tile', action='store_true',
-                    help='resident leg only (kernel A/B runs): value = the resident rate, not the headline metric')
+                    help='with --full: resident leg only (kernel A/B runs): value = the resident rate, not the headline metric')
     ap.add_argument('--tile-batch', type=int, default=6, help='chips per launch in the tile leg (6: 2.71-2.72M px/s vs 2.68-2.70M with 8, profiles/r04/tile_batch_ab.txt)')
     ap.add_argument('--tile-pool', type=int, default=64, help='generated chips behind the tile leg\'s chips (each position a date-shifted copy; ~18 GB of host memory per rank; 32 / 64 / 128: the same rate, profiles/r04/tile_pool_ab.txt)')
     ap.add_argument('--tile-contexts', type=int, default=4, help='contexts per GPU in the tile leg')
@@ -89,14 +113,15 @@ def parse():
                          '(never read by the detection; default) or only of fill observations (lossless)')
     ap.add_argument('--tile-depth', type=int, default=2, help='batches each tile-leg context keeps uploaded ahead')
     ap.add_argument('--tile-split', action='store_true',
-                    help='the north-star mode: ONE 2500-chip tile split over all ranks through the shared queue '
-                         '(strong scaling; value = the tile\'s pixels / its wall time) instead of one tile per rank')
+                    help='the north-star mode: the K steps\' chips (default ONE 2500-chip tile) split over all ranks '
+                         'through the shared queue (strong scaling; value = their pixels / the wall time) instead of '
+                         'K steps per rank')
     ap.add_argument('--no-north-star', action='store_true',
                     help='N > 1: skip the extra one-tile-over-all-ranks run reported as north_star_tile')
     ap.add_argument('--tile-parity-pixels', type=int, default=16,
-                    help='pixels per tile position re-detected by the C oracle after the timed tile run '
+                    help='--full: pixels per tile position re-detected by the C oracle after the timed tile run '
                          '(tile.parity_sample: 16 x 2500 = 4 x 10^4 pixels per tile, ~14 s of oracle time on 16 '
-                         'threads; 0 = none)')
+                         'threads; the last 2500 positions per rank of a longer run; 0 = none)')
     ap.add_argument('--roofline-launches', type=int, default=3,
                     help='single-context launches of the resident batch timed for the roofline (per-launch duration)')
     ap.add_argument('--no-config-legs', action='store_true',
@@ -105,7 +130,12 @@ def parse():
     ap.add_argument('--config-leg-steps', type=int, default=3, help='timed steps of each other-config resident leg')
     ap.add_argument('--share-device', action='store_true',
                     help='rehearsal only: ranks beyond the device count share devices (LOCAL_RANK mod count)')
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.no_tile and not args.full:
+        ap.error('--no-tile selects the resident leg, which is part of --full')
+    if args.no_tile and args.dump_outputs:
+        ap.error('--dump-outputs writes the tile leg\'s outputs (not with --no-tile)')
+    return args
 
 
 def chip_ids(rank, chips, world=1, n_obs_of=None):
@@ -194,7 +224,7 @@ def main():
     n_devices = min(world, ndev) if args.share_device else world
 
     if args.no_resident:
-        tl = tile_leg(args, cfg, rank, world, device, dist)
+        tl = tile_leg(args, cfg, rank, world, device, dist, dump=args.dump_outputs)
         if rank == 0:
             print(json.dumps({'metric': 'tile leg only (knob sweep)', 'value': tl['value'], 'unit': 'pixels/s',
                               'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': tl['ms_per_step'],
@@ -202,6 +232,14 @@ def main():
                                                     'tile_depth': args.tile_depth,
                                                     'HSA_ENABLE_SDMA': os.environ.get('HSA_ENABLE_SDMA')}}),
                   file=json_out, flush=True)
+        if dist is not None:
+            dist.destroy_process_group()
+        return
+    if not args.full:
+        # the plain run: the headline's tile leg and nothing else
+        tl = tile_leg(args, cfg, rank, world, device, dist, split=args.tile_split, dump=args.dump_outputs)
+        if rank == 0:
+            print(json.dumps(headline(args, tl, world, n_devices)), file=json_out, flush=True)
         if dist is not None:
             dist.destroy_process_group()
         return
@@ -219,7 +257,7 @@ def main():
         if dist is not None:
             dist.destroy_process_group()
         return
-    tl = tile_leg(args, cfg, rank, world, device, dist, split=args.tile_split)
+    tl = tile_leg(args, cfg, rank, world, device, dist, split=args.tile_split, dump=args.dump_outputs)
     north = None
     if world > 1 and not args.tile_split and not args.no_north_star:
         # the north-star target: one tile over all ranks (BASELINE.json north_star; core.py:97-108)
@@ -249,49 +287,8 @@ def main():
             r.pop('batch')
             others['resident_c%d' % k] = r
     if rank == 0:
-        out = {
-            'metric': 'pixels/sec change-detected (CONUS ARD tile) at 1/2/4/8 MI355X; FP64 VALU %',
-            'value': tl['value'],
-            'unit': 'pixels/s',
-            'n_gpus': n_devices,
-            'steps': args.steps,
-            'warmup': args.warmup,
-            'ms_per_step': tl['ms_per_step'],
-            'higher_is_better': True,
-            'scaling': 'strong' if args.tile_split else 'weak',
-            'vs_baseline': None,
-            'dtype': 'f64',
-            'data': 'synthetic (Landsat 4-8 ARD, seeded; tile leg: every chip distinct -- date-shifted copies of GPU-generated pool chips)',
-            'config': {
-                'workload': '%s; %s (%d distinct 100x100-pixel chips per rank, %s), '
-                            'PCIe-inclusive: chips uploaded from pinned host memory in the runner\'s transport encoding '
-                            '(%s), detected, segment/pixel rows packed '
-                            'on the device and fetched back, per-chip summaries gathered on rank 0 (ccdc.runner.changedetection); '
-                            'a step = %d chips per rank' % (
-                                CONFIG_NAMES[args.config],
-                                'ONE full 5000x5000-pixel tile split over all %d GPUs' % world if args.tile_split
-                                else 'one full 5000x5000-pixel tile per GPU', tl['chips_per_rank'],
-                                ', '.join('%d chips of %d obs' % (v, k) for k, v in sorted(tl['n_obs_mix'].items())),
-                                'raw upload' if args.tile_no_encode else
-                                'band values of fill/cloud/shadow observations, which the detection never reads, not sent'
-                                if args.tile_encode == 'unread' else 'lossless',
-                                tl['chips_per_step']),
-                'workload_key': 'tile%d_config%d_chips%d_pcie%s' % (args.tile_chips, args.config, tl['chips_per_rank'],
-                                                                   '_split' if args.tile_split else ''),
-                'synthetic_config': args.config,
-                'chips_per_gpu': tl['chips_per_rank'],
-                'pixels_per_chip': PIXELS_PER_CHIP,
-                'n_obs_mix': tl['n_obs_mix'],
-                'tile_chips': TILE_CHIPS,
-                'ranks': world,
-                'parallelism': 'chip-sharded x%d (one process per GPU, shared dynamic chip queue, no collective)' % world,
-                'tile_split': bool(args.tile_split),
-            },
-            'roofline': res['roofline'],
-            'value_resident': res['value'],
-            'resident': res,
-            'tile': tl,
-        }
+        out = headline(args, tl, world, n_devices)
+        out.update({'roofline': res['roofline'], 'value_resident': res['value'], 'resident': res})
         out.update(others)
         if north is not None:
             out['north_star_tile'] = {k: north.get(k) for k in (
@@ -319,6 +316,57 @@ def main():
         print(json.dumps(out), file=json_out, flush=True)
     if dist is not None:
         dist.destroy_process_group()
+
+
+def headline(args, tl, world, n_devices):
+    """The result line of the tile leg ``tl`` (rank 0): the headline fields and the leg's own
+    record; --full adds the roofline and the other legs to it."""
+    n = tl['steps'] * args.step_chips
+    extent = ('one full 5000x5000-pixel tile' if n == TILE_CHIPS else
+              '%d steps of %d chips of consecutive 5000x5000-pixel tiles' % (tl['steps'], args.step_chips))
+    return {
+        'metric': 'pixels/sec change-detected (CONUS ARD tile) at 1/2/4/8 MI355X; FP64 VALU %',
+        'value': tl['value'],
+        'unit': 'pixels/s',
+        'n_gpus': n_devices,
+        'steps': args.steps,
+        'warmup': args.warmup,
+        'ms_per_step': tl['ms_per_step'],
+        'higher_is_better': True,
+        'scaling': 'strong' if args.tile_split else 'weak',
+        'vs_baseline': None,
+        'dtype': 'f64',
+        'data': 'synthetic (Landsat 4-8 ARD, seeded; tile leg: every chip distinct -- date-shifted copies of GPU-generated pool chips)',
+        'config': {
+            'workload': '%s; %s (%d distinct 100x100-pixel chips per rank, %s), '
+                        'PCIe-inclusive: chips uploaded from pinned host memory in the runner\'s transport encoding '
+                        '(%s), detected, segment/pixel rows packed '
+                        'on the device and fetched back, per-chip summaries gathered on rank 0 (ccdc.runner.changedetection); '
+                        'a step = %d chips per rank' % (
+                            CONFIG_NAMES[args.config],
+                            '%s split over all %d GPUs' % (extent.replace('one', 'ONE'), world) if args.tile_split
+                            else '%s per GPU' % extent, tl['chips_per_rank'],
+                            ', '.join('%d chips of %d obs' % (v, k) for k, v in sorted(tl['n_obs_mix'].items())),
+                            'raw upload' if args.tile_no_encode else
+                            'band values of fill/cloud/shadow observations, which the detection never reads, not sent'
+                            if args.tile_encode == 'unread' else 'lossless',
+                            tl['chips_per_step']),
+            'workload_key': 'tile%d_config%d_chips%d_pcie%s' % (n, args.config,
+                                                               tl['chips_per_rank'], '_split' if args.tile_split else ''),
+            'synthetic_config': args.config,
+            'chips_per_gpu': tl['chips_per_rank'],
+            'pixels_per_chip': PIXELS_PER_CHIP,
+            'n_obs_mix': tl['n_obs_mix'],
+            'tile_chips': TILE_CHIPS,
+            'ranks': world,
+            'parallelism': 'chip-sharded x%d (one process per GPU, shared dynamic chip queue, no collective)' % world,
+            'tile_split': bool(args.tile_split),
+        },
+        'roofline': None,
+        'full': bool(args.full),
+        'outputs_dumped': tl.get('outputs_dumped'),
+        'tile': tl,
+    }
 
 
 def resident_leg(args, cfg, rank, world, device, dist, batch=None):
@@ -621,26 +669,43 @@ class _KeptContext(object):
         pass
 
 
-def tile_leg(args, cfg, rank, world, device, dist, split=False):
-    """The headline: ``--tile-chips`` distinct chips per rank (default one full 2500-chip tile)
-    through ccdc.runner.changedetection with chips generated on the GPU into pinned host memory
-    (ccdgpu.synth.TileSource).  Positions 0 .. world * tile_chips - 1 share one dynamic queue;
+def sample_pixels(pos, k):
+    """The ``k`` pixels of the chip at tile position ``pos`` that the parity sample and the output
+    dump keep (fixed by the position: the same from run to run)."""
+    return sorted({(int(pos) * 7919 + 13 + j * 1009) % PIXELS_PER_CHIP for j in range(k)})
+
+
+def tile_leg(args, cfg, rank, world, device, dist, split=False, dump=None):
+    """The headline: K = ``--steps`` steps of ``--step-chips`` distinct chips per rank (default 5 x
+    500: one full 2500-chip tile) through ccdc.runner.changedetection with chips generated on the
+    GPU into pinned host memory (ccdgpu.synth.TileSource).  All ranks' positions share one queue;
     position p is generator chip p (tile p // 2500, chip p % 2500 of it; coordinates on the
     reference grid of test/data/tile_response.json shifted one tile width per tile).  W warmup
     steps run first on chips of a separate tile range (positions offset by 10^6).  ``split``: the
-    north-star mode -- ONE tile of ``--tile-chips`` positions over all ranks (strong scaling).
-    After the timed run, ``--tile-parity-pixels`` pixels of every position are re-detected by the
-    C oracle from the position's raw inputs (tests/tile_sample.py; the checker, outside the timing)
-    and reported as ``parity_sample``."""
+    north-star mode -- the K steps' positions (default ONE tile) over all ranks (strong scaling).
+    With --full, after the timed run, ``--tile-parity-pixels`` pixels of every position (of the
+    last 2500 per rank) are re-detected by the C oracle from the position's raw inputs
+    (tests/tile_sample.py; the checker, outside the timing) and reported as ``parity_sample``.
+    ``dump``: a directory for the last step's outputs (dump_outputs)."""
     import ccdgpu
     from ccdc import runner
     from ccdgpu import synth
     B = args.tile_batch
     K = max(1, args.steps)
-    total = int(args.tile_chips) if split else world * int(args.tile_chips)
+    total = K * int(args.step_chips) * (1 if split else world)
     per_rank = -(-total // world)
     chips_per_step = -(-per_rank // K)
-    warm_total = world * min(per_rank, args.warmup * chips_per_step)
+    warm_total = world * args.warmup * chips_per_step
+    # positions whose sampled pixels the sink keeps: for the oracle (--full) and for the dump
+    n_parity = int(args.tile_parity_pixels) if args.full else 0
+    parity_from = max(0, total - world * TILE_CHIPS)
+    dump_from = max(0, total - min(world * chips_per_step, DUMP_CHIPS))
+
+    def kept_pixels(pos):
+        keep = sample_pixels(pos, n_parity) if pos >= parity_from else []
+        if dump and pos >= dump_from:
+            keep = sorted(set(keep) | set(sample_pixels(pos, DUMP_PIXELS)))
+        return keep
     # distinct chips: a pool of generated chips, each position a different rotation of one of them
     # (configs 3 / 5, whose chips share two date vectors); configs 2 / 4 subsample dates per chip,
     # so there every chip is generated on the GPU
@@ -684,12 +749,10 @@ def tile_leg(args, cfg, rank, world, device, dist, split=False):
         nonlocal lent
         lent = iter(ctxs)
         sink = runner.SummarySink(digest=False)
-        if sample and args.tile_parity_pixels > 0:
+        if sample and (n_parity > 0 or dump):
             sys.path.insert(0, os.path.join(ROOT, 'tests'))
             import tile_sample
-            k = int(args.tile_parity_pixels)
-            sink = sample_sink[0] = tile_sample.PixelSampleSink(
-                lambda pos: sorted({(int(pos) * 7919 + 13 + j * 1009) % PIXELS_PER_CHIP for j in range(k)}), sink)
+            sink = sample_sink[0] = tile_sample.PixelSampleSink(kept_pixels, sink)
         xys = [xy(p) for p in range(n)]
         # (encode=False: the source is already the encoding wrapper when the leg encodes)
         return runner.changedetection(xys, src, device=device, contexts=args.tile_contexts, batch_chips=B,
@@ -713,9 +776,18 @@ def tile_leg(args, cfg, rank, world, device, dist, split=False):
     el = max_over_ranks(time.perf_counter() - t, dist)
     thread_cpu = tcpu.stop()
     cg1 = _cgroup_cpu()  # (before the parity checker: its oracle threads are not the tile's CPU)
-    parity = None
+    parity = dumped = None
     if sample_sink[0] is not None:
-        parity = tile_parity_sample(sample_sink[0], src, cfg, mode, dist)
+        samples = sample_sink[0].samples
+        for p in [p for p, s in samples.items() if not s[3]]:
+            del samples[p]  # (positions outside both samples)
+        if dump:
+            parts = runner.gather({p: s for p, s in samples.items() if p >= dump_from}, dist)
+            if parts is not None and res is not None:
+                dumped = dump_outputs(dump, {p: s for part in parts for p, s in part.items()},
+                                      [c for c in res['chips'] if c['pos'] >= dump_from])
+        if n_parity > 0:
+            parity = tile_parity_sample(sample_sink[0], src, cfg, mode, dist)
     gen_s = src.generate_seconds - gen0
     cg = None
     if cg0 and cg1:
@@ -742,7 +814,7 @@ def tile_leg(args, cfg, rank, world, device, dist, split=False):
         mix[c['n_obs']] = mix.get(c['n_obs'], 0) + 1
     ranks = {st['rank']: st for st in res['ranks']}
     return {'value': px / el, 'unit': 'pixels/s', 'seconds': el, 'ms_per_step': el / K * 1e3, 'steps': K,
-            'split': bool(split), 'parity_sample': parity,
+            'split': bool(split), 'parity_sample': parity, 'outputs_dumped': dumped,
             'chips_per_step': chips_per_step, 'chips_per_rank': per_rank, 'chips': len(res['chips']), 'pixels': px,
             'distinct_chips': len(res['chips']), 'chips_per_launch': B, 'contexts_per_gpu': args.tile_contexts,
             'upload_depth': args.tile_depth, 'ranks': world, 'n_obs_mix': mix,
@@ -771,6 +843,49 @@ def tile_leg(args, cfg, rank, world, device, dist, split=False):
                                             'never read by the detection, results identical'
                                             if args.tile_encode == 'unread' else 'lossless')
                     if encode else 'chips copied into pinned batches by the runner\'s fetch threads, uploaded raw')}
+
+
+def dump_outputs(directory, samples, summaries):
+    """--dump-outputs: what the timed changedetection call computed in its last step, as float64
+    arrays (every field is an int32, a uint32 or a float32: exact in float64), ordered by tile
+    position and pixel.  ``samples``: PixelSampleSink.samples of the step's positions (the rows
+    and mask words the call handed its sink for DUMP_PIXELS pixels of each chip); ``summaries``:
+    the step's per-chip summaries in the call's return value.
+      rows.npy            [n_rows][78]  the device-packed rows (abi.ROW_DTYPE fields in order,
+                                        array fields flattened)
+      row_index.npy       [n_rows][2]   tile position, pixel of each row
+      mask_words.npy      [n_pixels][w] processing-mask bit words (zero-padded to the longest)
+      mask_index.npy      [n_pixels][3] tile position, pixel, observations of each mask row
+      chip_summaries.npy  [n_chips][7]  pos, cx, cy, n_pix, n_obs, rows, models of every chip
+    Returns {'directory', 'bytes', 'arrays': {name: shape}}."""
+    from ccdgpu import abi
+    names = abi.ROW_DTYPE.names
+    rows, row_index, masks, mask_index = [], [], [], []
+    for pos in sorted(samples):
+        _, _, n_obs, keep = samples[pos]
+        want = set(sample_pixels(pos, DUMP_PIXELS))
+        for px in sorted(p for p in keep if p in want):
+            r, m = keep[px]
+            rows.append(np.concatenate([r[f].reshape(r.shape[0], -1).astype(np.float64) for f in names], axis=1))
+            row_index += [(pos, px)] * r.shape[0]
+            masks.append(np.asarray(m, dtype='<u4').astype(np.float64).ravel())
+            mask_index.append((pos, px, n_obs))
+    width = max([m.shape[0] for m in masks] + [0])
+    arrays = {
+        'rows': np.concatenate(rows, axis=0) if rows else np.zeros((0, 0)),
+        'row_index': np.array(row_index, dtype=np.float64).reshape(-1, 2),
+        'mask_words': np.array([np.pad(m, (0, width - m.shape[0])) for m in masks], dtype=np.float64).reshape(-1, width),
+        'mask_index': np.array(mask_index, dtype=np.float64).reshape(-1, 3),
+        'chip_summaries': np.array([[c[k] for k in ('pos', 'cx', 'cy', 'n_pix', 'n_obs', 'rows', 'models')]
+                                    for c in sorted(summaries, key=lambda c: c['pos'])], dtype=np.float64).reshape(-1, 7),
+    }
+    size = sum(a.nbytes for a in arrays.values())
+    if size > DUMP_MAX_BYTES:
+        raise SystemExit('--dump-outputs: %d bytes exceed the %d-byte bound (fewer --step-chips)' % (size, DUMP_MAX_BYTES))
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + '.npy'), a)
+    return {'directory': directory, 'bytes': size, 'arrays': {k: list(a.shape) for k, a in arrays.items()}}
 
 
 def tile_parity_sample(sink, src, cfg, mode, dist):

@@ -6,7 +6,7 @@ set -o pipefail
 TAG=${1:-ev}
 R=$(pwd); O=$R/gpurun_out/$TAG; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/stats -o run -- python3 $R/bench.py --no-tile --no-packer --no-cpu-baseline --contexts 1 --steps 6 --warmup 1 --roofline-launches 3 > $O/stats_bench.json 2> $O/stats_bench.err || { echo "stats rc=$?"; tail -5 $O/stats_bench.err; exit 1; }
+timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/stats -o run -- python3 $R/bench.py --full --no-tile --no-packer --no-cpu-baseline --contexts 1 --steps 6 --warmup 1 --roofline-launches 3 > $O/stats_bench.json 2> $O/stats_bench.err || { echo "stats rc=$?"; tail -5 $O/stats_bench.err; exit 1; }
 cd $R
 python3 tools/rocpd_stats.py $O/stats/run_results.db $O/kernel_stats.csv && head -4 $O/kernel_stats.csv
 python3 -c "import json; d=json.load(open('$O/stats_bench.json')); r=d['roofline']; print('stats run: frac', round(r['frac'],4), 'launch_ms', round(r['kernel_ms_per_launch'],2), r['kernel_ms_single_context_launches'])"
