@@ -312,6 +312,63 @@ int ccdgpu_fetch_batch_rows_into(ccdgpu_ctx *ctx, const int32_t *cx, const int32
                                  uint32_t *mask_bits, int64_t mask_cap, int64_t *n_rows);
 void ccdgpu_rows_free(ccdgpu_rows *out);
 
+/* Random-forest classification of segment rows: the `rfrawp` column of the segment table
+ * (resources/schema.cql segment.rfrawp; the reference fills it with Spark ML's
+ * RandomForestClassificationModel.rawPrediction, ccdc/randomforest.py:25-39, 500 trees).  Only
+ * inference of an imported forest; training stays with Spark.
+ *
+ * A forest is plain arrays over one node pool.  For one row x[n_features]:
+ *     raw[:] = 0.0 (double)
+ *     for t = 0 .. n_trees-1, in this order:
+ *         n = root[t]
+ *         while feature[n] >= 0:  n = (x[feature[n]] <= threshold[n]) ? left[n] : right[n]
+ *         raw[:] += value[n][:]                       (double adds, in tree order)
+ *     out[:] = (float) raw[:]                         (round to nearest)
+ * A NaN feature value compares false and goes right.  value[] holds the leaves' normalised class
+ * distributions (Spark's rawPrediction sums them); the library does not renormalise.  The result
+ * of a row does not depend on how rows are batched or launched. */
+#define CCDGPU_FOREST_MAX_FEATURES 64
+#define CCDGPU_FOREST_MAX_CLASSES 32
+typedef struct ccdgpu_forest {
+    int32_t n_trees, n_nodes;
+    int32_t n_features;         /* 1 .. CCDGPU_FOREST_MAX_FEATURES                          */
+    int32_t n_classes;          /* 1 .. CCDGPU_FOREST_MAX_CLASSES                           */
+    const int32_t *root;        /* [n_trees] node index of each tree's root                 */
+    const int32_t *feature;     /* [n_nodes] feature tested at the node; < 0 marks a leaf   */
+    const double *threshold;    /* [n_nodes]                                                */
+    const int32_t *left;        /* [n_nodes] child for x[feature] <= threshold              */
+    const int32_t *right;       /* [n_nodes] child otherwise                                */
+    const double *value;        /* [n_nodes][n_classes], read at leaves only                */
+} ccdgpu_forest;
+/* The checks every forest passes before it reaches the device (no device needed).  0, or
+ * CCDGPU_EINVAL with the reason in ccdgpu_last_error(): sizes outside the limits; a root or child
+ * index outside [0, n_nodes); a child index not strictly greater than its parent's (every walk is
+ * then finite; sklearn's and Spark's pre-order numbering satisfy it); a node with two parents (or
+ * a root that is also a child or another tree's root); an internal node's feature >= n_features;
+ * a non-finite threshold at an internal node; a non-finite leaf value.  ccdgpu_forest_depth does
+ * the same and returns the largest number of branches from a root to a leaf. */
+int ccdgpu_forest_check(const ccdgpu_forest *f);
+int ccdgpu_forest_depth(const ccdgpu_forest *f, int32_t *max_depth);
+/* Check `f`, upload it and make it the context's forest (the arrays are not needed afterwards);
+ * a previous forest is replaced and freed, ccdgpu_destroy frees it, ccdgpu_forest_clear removes
+ * it.  The detection entry points are unaffected by a forest. */
+int ccdgpu_forest_set(ccdgpu_ctx *ctx, const ccdgpu_forest *f);
+int ccdgpu_forest_clear(ccdgpu_ctx *ctx);
+/* Host-matrix path: features [n_rows][n_features] (what ccdc.features.matrix returns) ->
+ * rfrawp [n_rows][n_classes].  Synchronous; *kernel_seconds (may be NULL) gets the device time of
+ * the forest kernel.  n_rows == 0 succeeds without a launch; CCDGPU_EINVAL with no forest set. */
+int ccdgpu_classify(ccdgpu_ctx *ctx, const double *features, int64_t n_rows, float *rfrawp, double *kernel_seconds);
+/* Chained path (needs n_features == 33): classify the rows of the context's last completed run,
+ * in exactly the order and count ccdgpu_fetch_batch_rows_into returns them, without the rows
+ * leaving the device.  aux [total_pixels][5]: dem, aspect, slope, mpw, posidex of each pixel of
+ * the batch.  The feature vector of a row is ccdc.features.columns(): mag[0..6], rmse[0..6],
+ * coef[b][0] for b = 0..6, intercept[0..6] -- the row's float32 values widened to double -- then
+ * the pixel's 5 aux values.  A row with has_model == 0 (pyccd.default's row) is not walked and
+ * gets NaN in every class.  *n_rows is always set; with rows_cap too small CCDGPU_EINVAL and
+ * nothing is written (grow and call again). */
+int ccdgpu_classify_rows(ccdgpu_ctx *ctx, const double *aux, float *rfrawp, int64_t rows_cap, int64_t *n_rows,
+                         double *kernel_seconds);
+
 /* Kernel statistics of the last run (per launch of the main detection kernel). */
 typedef struct ccdgpu_stats {
     double detect_ms;           /* average duration of the detection kernel (HIP events)   */

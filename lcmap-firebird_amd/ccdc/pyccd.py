@@ -234,12 +234,13 @@ def detect_partition(records, params=None):
     return rows
 
 
-def _run_chips(chips, params, context, symmetric=True):
+def _run_chips(chips, params, context, symmetric=True, on_batch=None):
     """Group chipmunk chips by location, batch locations that share a date vector, stage each
     batch with the device chip packer and detect it.  Yields (ctx, chip index, (cx, cy),
     dates [n] int64 descending, n_pix) for every location, batch by batch.  symmetric=False
     accepts locations whose layers lack some dates (they stage as fill, QA 1) instead of
-    raising like merlin's symmetric date check."""
+    raising like merlin's symmetric date check.  on_batch(ctx, keys, n_pix), when given, is
+    called after each batch's detection with the batch's locations in chip order."""
     import ccdgpu
     from ccdc import chipmunk
     groups = chipmunk.group(chips)
@@ -254,6 +255,8 @@ def _run_chips(chips, params, context, symmetric=True):
         n_pix = chipmunk.payload_pixels(first_payload)
         ctx.stage_chipmunk(dates, text, offsets, n_pix, params)
         ctx.run()
+        if on_batch is not None:
+            on_batch(ctx, [key for key, _ in members], n_pix)
         for c, (key, _) in enumerate(members):
             yield ctx, c, key, dates[0], n_pix
 

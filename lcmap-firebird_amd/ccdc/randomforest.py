@@ -1,0 +1,175 @@
+"""ccdc.randomforest -- random-forest classification of segments: the ``rfrawp`` column
+(Spark-free mirror of the inference half of reference ccdc/randomforest.py).
+
+The reference trains a Spark ML RandomForestClassifier (500 trees, randomforest.py:25-39) on
+``features.dataframe`` and keeps the model's ``rawPrediction`` per segment as ``rfrawp``
+(array<float>; ``segment.join`` puts it on the segment rows).  Training stays with Spark.  Here an
+imported forest -- plain arrays, see include/ccdgpu.h -- is evaluated on the device
+(ccd_forest.hip through ``ccdgpu.Context.classify`` / ``classify_rows``); there is no CPU path.
+
+rawPrediction of a row is the sum over the trees, in tree order, of the reached leaf's normalised
+class distribution, indexed by label.  A Spark ``RandomForestClassificationModel`` maps to the
+arrays tree by tree (``model.trees``): an InternalNode gives ``feature = split.featureIndex``,
+``threshold = split.threshold`` (ContinuousSplit: ``x <= threshold`` goes left) and its two
+children; a LeafNode gives ``feature = -1`` and ``value = impurityStats.stats / sum(stats)``;
+numbering each tree's nodes in pre-order satisfies the child > parent rule of the check.
+"""
+import ctypes
+
+import numpy as np
+import pyarrow as pa
+import pyarrow.compute as pc
+
+from ccdc import features
+
+KEYS = ['cx', 'cy', 'px', 'py', 'sday', 'eday']
+_ARRAYS = ('root', 'feature', 'threshold', 'left', 'right', 'value')
+
+
+class Forest(object):
+    """A forest as the arrays of ccdgpu_forest: root [n_trees], feature / threshold / left /
+    right [n_nodes] (feature < 0 marks a leaf), value [n_nodes][n_classes] (leaves' normalised
+    class distributions)."""
+
+    def __init__(self, root, feature, threshold, left, right, value, n_features):
+        from ccdgpu import abi
+        self._struct, arrays = abi.forest_struct(root, feature, threshold, left, right, value, n_features)
+        self.root, self.feature, self.threshold, self.left, self.right, self.value = arrays
+        self.n_features = int(n_features)
+
+    n_trees = property(lambda self: int(self.root.shape[0]))
+    n_nodes = property(lambda self: int(self.feature.shape[0]))
+    n_classes = property(lambda self: int(self.value.shape[1]))
+
+    def struct(self):
+        """The abi.Forest over this forest's arrays (valid while the forest is alive)."""
+        return self._struct
+
+    def check(self):
+        """ccdgpu_forest_check (no device needed): ValueError with the library's message."""
+        import ccdgpu
+        if ccdgpu.lib().ccdgpu_forest_check(ctypes.byref(self._struct)) != 0:
+            raise ValueError(ccdgpu.last_error())
+        return self
+
+    @property
+    def max_depth(self):
+        """Branches from a root to the deepest leaf (ccdgpu_forest_depth)."""
+        import ccdgpu
+        d = ctypes.c_int32(0)
+        if ccdgpu.lib().ccdgpu_forest_depth(ctypes.byref(self._struct), ctypes.byref(d)) != 0:
+            raise ValueError(ccdgpu.last_error())
+        return d.value
+
+    @classmethod
+    def from_arrays(cls, root, feature, threshold, left, right, value, n_features):
+        """Forest from array-likes, validated by the library's check."""
+        return cls(root, feature, threshold, left, right, value, n_features).check()
+
+    @classmethod
+    def from_sklearn(cls, rf):
+        """Forest of a fitted sklearn RandomForestClassifier (or any ensemble of single-output
+        DecisionTreeClassifiers in ``estimators_``).  The class vector is Spark's, indexed by
+        label: ``classes_`` must be non-negative integers, n_classes = max(label) + 1, labels the
+        training set lacks are zero columns."""
+        classes = np.asarray(rf.classes_)
+        if classes.ndim != 1 or getattr(rf, 'n_outputs_', 1) != 1:
+            raise ValueError('from_sklearn needs a single-output classifier')
+        if classes.dtype.kind == 'b' or not (classes.dtype.kind in 'iu' or
+                                             (classes.dtype.kind == 'f' and np.all(classes == np.floor(classes)))):
+            raise ValueError('class labels must be non-negative integers, got %r' % (classes.tolist(),))
+        labels = classes.astype(np.int64)
+        if labels.size == 0 or labels.min() < 0:
+            raise ValueError('class labels must be non-negative integers, got %r' % (classes.tolist(),))
+        n_classes = int(labels.max()) + 1
+        root, feature, threshold, left, right, value = [], [], [], [], [], []
+        base = 0
+        for est in rf.estimators_:
+            t = est.tree_
+            n = int(t.node_count)
+            leaf = t.children_left[:n] < 0
+            v = np.asarray(t.value[:n, 0, :], dtype=np.float64)
+            if v.shape[1] != labels.size:
+                raise ValueError('a tree has %d classes, the ensemble %d' % (v.shape[1], labels.size))
+            v = v / v.sum(axis=1, keepdims=True)
+            full = np.zeros((n, n_classes), dtype=np.float64)
+            full[:, labels] = v
+            root.append(base)
+            feature.append(np.where(leaf, -1, t.feature[:n]).astype(np.int32))
+            threshold.append(np.where(leaf, 0.0, t.threshold[:n]))
+            left.append(np.where(leaf, -1, t.children_left[:n] + base).astype(np.int32))
+            right.append(np.where(leaf, -1, t.children_right[:n] + base).astype(np.int32))
+            value.append(full)
+            base += n
+        return cls.from_arrays(np.asarray(root, np.int32), np.concatenate(feature), np.concatenate(threshold),
+                               np.concatenate(left), np.concatenate(right), np.concatenate(value),
+                               int(rf.n_features_in_))
+
+    def save(self, path):
+        """Write the arrays as .npz (``path`` as given to numpy.savez: a name gets '.npz')."""
+        np.savez(path, n_features=np.int32(self.n_features), **{k: getattr(self, k) for k in _ARRAYS})
+
+    @classmethod
+    def load(cls, path):
+        with np.load(path) as z:
+            return cls.from_arrays(*[z[k] for k in _ARRAYS], n_features=int(z['n_features']))
+
+
+def _context(context):
+    import ccdgpu
+    return context or ccdgpu.default_context()
+
+
+def predictions(aux, segments, forest, context=None):
+    """Raw predictions of the segments that have a model: an Arrow table cx, cy, px, py, sday,
+    eday, rfrawp (the reference's predictions dataframe, joined to the segments by ``join``).
+    The features are ``features.join`` / ``independent`` / ``matrix`` of the aux and segment
+    tables; the forest runs on the device (``Context.classify``)."""
+    t = features.join({'aux': aux, 'ccd': segments})
+    t = t.filter(pc.is_valid(t['chprob']))  # pyccd.default's rows have no model to classify
+    ctx = _context(context)
+    ctx.set_forest(forest)
+    raw = ctx.classify(features.matrix(features.independent(t)))
+    from ccdc import sink
+    return t.select(KEYS).append_column('rfrawp', sink._list_col(raw, np.ones(raw.shape[0], dtype=bool)))
+
+
+def join(segments, predictions):
+    """Arrow counterpart of segment.join (segment.py:103-116): inner join on cx, cy, px, py,
+    sday, eday; the segments' rfrawp column replaced by the predictions'.  Rows keep the
+    segments' order."""
+    s = segments.select(KEYS).append_column('_s', pa.array(np.arange(segments.num_rows, dtype=np.int64)))
+    p = predictions.select(KEYS).cast(segments.select(KEYS).schema)  # (a table built elsewhere: the segments' key types)
+    p = p.append_column('_p', pa.array(np.arange(predictions.num_rows, dtype=np.int64)))
+    j = s.join(p, keys=KEYS, join_type='inner').sort_by([('_s', 'ascending')])
+    out = segments.take(j['_s'])
+    raw = predictions['rfrawp'].take(j['_p'])
+    i = out.schema.get_field_index('rfrawp')
+    return out.set_column(i, out.schema.field(i), pc.cast(raw, out.schema.field(i).type))
+
+
+def classify_chips_tables(chips, aux_of, forest, params=None, context=None, width=100):
+    """``pyccd.detect_chips_tables`` with the segment tables' rfrawp filled: each batch's rows are
+    gathered into feature vectors and classified on the device right behind its detection
+    (``Context.classify_rows``), rows without a model staying null.  aux_of(cx, cy) gives the
+    chip's [n_pix][5] aux values (dem, aspect, slope, mpw, posidex), pixels in row-major order."""
+    import ccdgpu
+    from ccdc import pyccd, sink
+    ctx = _context(context)
+    ctx.set_forest(forest)
+    state = {}
+
+    def on_batch(ctx, keys, n_pix):
+        aux = np.concatenate([np.asarray(aux_of(cx, cy), dtype=np.float64).reshape(n_pix, 5) for cx, cy in keys])
+        state['raw'], state['at'] = ctx.classify_rows(aux), 0
+
+    out = []
+    for ctx, c, (cx, cy), dates, n_pix in pyccd._run_chips(chips, params, ctx, on_batch=on_batch):
+        u = ctx.fetch(c)  # procedure / QA error check
+        if u.error_pixel >= 0:
+            raise ccdgpu.QAValueError('unsupported QA value at pixel %d of chip (%d, %d)' % (u.error_pixel, cx, cy))
+        off, rows, mask = ctx.fetch_rows(c, cx, cy, width)
+        a = state['at']
+        state['at'] = a + rows.shape[0]  # the batch's rows are chip-major
+        out.append(((cx, cy), sink.tables(cx, cy, dates, off, rows, mask, rfrawp=state['raw'][a:a + rows.shape[0]])))
+    return out

@@ -60,7 +60,19 @@ def _list_col(values, valid):
     return lst
 
 
-def _row_columns(cx, cy, rows):
+def _rfrawp_col(n, rfrawp):
+    """The rfrawp column: null without predictions (as the detection writes it), else
+    [n][n_classes] float32 (ccdc.randomforest) with all-NaN rows -- rows without a model, which
+    are not classified -- null."""
+    if rfrawp is None:
+        return pa.nulls(n, type=pa.list_(pa.float32()))
+    v = np.ascontiguousarray(rfrawp, dtype=np.float32)
+    if v.ndim != 2 or v.shape[0] != n:
+        raise ValueError('rfrawp must be [%d][n_classes], got %r' % (n, v.shape))
+    return _list_col(v, ~np.isnan(v).any(axis=1))
+
+
+def _row_columns(cx, cy, rows, rfrawp=None):
     """Columns shared by the ccd and segment tables (pyccd.format keys, pyccd.py:106-145)."""
     n = rows.shape[0]
     valid = rows['has_model'] != 0
@@ -80,7 +92,7 @@ def _row_columns(cx, cy, rows):
         cols[pre + 'rmse'] = _float_col(rows['rmse'][:, b], valid)
         cols[pre + 'coef'] = _list_col(rows['coef'][:, b, :], valid)
         cols[pre + 'int'] = _float_col(rows['intercept'][:, b], valid)
-    cols['rfrawp'] = pa.nulls(n, type=pa.list_(pa.float32()))
+    cols['rfrawp'] = _rfrawp_col(n, rfrawp)
     return cols
 
 
@@ -96,9 +108,10 @@ def _build(spark_schema, cols):
     return pa.table([cols[f.name] for f in schema], schema=schema)
 
 
-def segment_table(cx, cy, rows):
-    """segment table (segment.schema(), segment.py:16-55): one row per change model."""
-    return _build(segment_mod.schema(), _row_columns(cx, cy, rows))
+def segment_table(cx, cy, rows, rfrawp=None):
+    """segment table (segment.schema(), segment.py:16-55): one row per change model.  rfrawp:
+    the rows' raw forest predictions [n_rows][n_classes] (NaN rows become null); null without."""
+    return _build(segment_mod.schema(), _row_columns(cx, cy, rows, rfrawp))
 
 
 def pixel_table(cx, cy, row_offsets, rows, mask):
@@ -131,9 +144,10 @@ def ccd_table(cx, cy, dates, row_offsets, rows, mask):
     return _build(pyccd_mod.schema(), cols)
 
 
-def tables(cx, cy, dates, row_offsets, rows, mask):
-    """{'segment', 'pixel', 'chip'} Arrow tables of one chip (the reference's Cassandra tables)."""
-    return {'segment': segment_table(cx, cy, rows),
+def tables(cx, cy, dates, row_offsets, rows, mask, rfrawp=None):
+    """{'segment', 'pixel', 'chip'} Arrow tables of one chip (the reference's Cassandra tables);
+    rfrawp as for segment_table."""
+    return {'segment': segment_table(cx, cy, rows, rfrawp),
             'pixel': pixel_table(cx, cy, row_offsets, rows, mask),
             'chip': chip_table(cx, cy, dates)}
 

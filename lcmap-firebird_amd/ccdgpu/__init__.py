@@ -77,6 +77,19 @@ def _declare(L):
         L.ccdgpu_device_numa_node.argtypes = [c.c_int, c.POINTER(c.c_int)]
         L.ccdgpu_device_numa_node.restype = c.c_int
     L.ccdgpu_synchronize.argtypes = [c.c_void_p]
+    L.ccdgpu_forest_check.argtypes = [c.POINTER(abi.Forest)]
+    L.ccdgpu_forest_check.restype = c.c_int
+    L.ccdgpu_forest_depth.argtypes = [c.POINTER(abi.Forest), c.POINTER(c.c_int32)]
+    L.ccdgpu_forest_depth.restype = c.c_int
+    L.ccdgpu_forest_set.argtypes = [c.c_void_p, c.POINTER(abi.Forest)]
+    L.ccdgpu_forest_set.restype = c.c_int
+    L.ccdgpu_forest_clear.argtypes = [c.c_void_p]
+    L.ccdgpu_forest_clear.restype = c.c_int
+    L.ccdgpu_classify.argtypes = [c.c_void_p, c.c_void_p, c.c_int64, c.c_void_p, c.POINTER(c.c_double)]
+    L.ccdgpu_classify.restype = c.c_int
+    L.ccdgpu_classify_rows.argtypes = [c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64, c.POINTER(c.c_int64),
+                                       c.POINTER(c.c_double)]
+    L.ccdgpu_classify_rows.restype = c.c_int
     L.ccdgpu_detect_batch.argtypes = [c.c_void_p, c.POINTER(abi.Params), c.c_int32, c.c_int32,
                                       c.c_void_p, c.c_void_p, c.c_void_p, c.POINTER(abi.Result)]
     L.ccdgpu_result_free.argtypes = [c.POINTER(abi.Result)]
@@ -121,7 +134,9 @@ EXPORTS = ('ccdgpu_version', 'ccdgpu_last_error', 'ccdgpu_params_default', 'ccdg
            'ccdgpu_fetch_batch_rows', 'ccdgpu_device_numa_node', 'ccdgpu_encoded_bound', 'ccdgpu_encode_chips',
            'ccdgpu_encode_vector_path', 'ccdgpu_stage_slot_encoded', 'ccdgpu_init_copy_cus',
            'ccdgpu_run_slot_begin', 'ccdgpu_run_query', 'ccdgpu_run_slot_end', 'ccdgpu_fetch_batch_rows_into',
-           'ccdgpu_run_slot_begin_rows', 'ccdgpu_run_slot_end_rows', 'ccdgpu_encoded_check')
+           'ccdgpu_run_slot_begin_rows', 'ccdgpu_run_slot_end_rows', 'ccdgpu_encoded_check',
+           'ccdgpu_forest_check', 'ccdgpu_forest_depth', 'ccdgpu_forest_set', 'ccdgpu_forest_clear',
+           'ccdgpu_classify', 'ccdgpu_classify_rows')
 
 
 def lib():
@@ -704,6 +719,78 @@ class Context(object):
             return abi.unpack_rows(r)
         finally:
             lib().ccdgpu_rows_free(ctypes.byref(r))
+
+    # random-forest classification of segment rows (rfrawp) --------------------------------------
+    def set_forest(self, forest):
+        """Make ``forest`` (an abi.Forest, or anything with ``.struct()`` giving one -- a
+        ccdc.randomforest.Forest) the context's forest: checked, uploaded, replacing any previous
+        one (ccdgpu_forest_set).  Raises ValueError for a forest that fails the check."""
+        f = forest if isinstance(forest, abi.Forest) else forest.struct()
+        rc = lib().ccdgpu_forest_set(self._ctx, ctypes.byref(f))
+        if rc == abi.E_INVAL:
+            raise ValueError(last_error())
+        _check(rc)
+        self._forest_shape = (int(f.n_features), int(f.n_classes))
+        self.forest_seconds = 0.0
+
+    def clear_forest(self):
+        _check(lib().ccdgpu_forest_clear(self._ctx))
+        self._forest_shape = None
+
+    def classify(self, features):
+        """features [n_rows][n_features] float64 (ccdc.features.matrix) -> rfrawp float32
+        [n_rows][n_classes] (ccdgpu_classify); the kernel seconds are in ``forest_seconds``."""
+        shape = getattr(self, '_forest_shape', None)
+        if shape is None:
+            raise CcdGpuError(abi.E_INVAL, 'no forest set (Context.set_forest)')
+        nf, nc = shape
+        x = np.ascontiguousarray(features, dtype=np.float64)
+        if x.ndim != 2 or x.shape[1] != nf:
+            raise ValueError('features must be [n_rows][%d], got %r' % (nf, x.shape))
+        out = np.empty((x.shape[0], nc), dtype=np.float32)
+        secs = ctypes.c_double(0.0)
+        _check(lib().ccdgpu_classify(self._ctx, x.ctypes.data, x.shape[0], out.ctypes.data, ctypes.byref(secs)))
+        self.forest_seconds = secs.value
+        return out
+
+    def classify_rows(self, aux, rows_cap=None):
+        """rfrawp float32 [n_rows][n_classes] of the rows of the last completed run, in the order
+        fetch_batch_rows_into / fetch_rows give them, gathered and classified on the device
+        (ccdgpu_classify_rows).  aux [total_pixels][5] float64: dem, aspect, slope, mpw, posidex.
+        Rows without a model are NaN.  ``rows_cap`` (tests): the buffer's room instead of a size
+        learned from the library."""
+        shape = getattr(self, '_forest_shape', None)
+        if shape is None:
+            raise CcdGpuError(abi.E_INVAL, 'no forest set (Context.set_forest)')
+        nc = shape[1]
+        a = np.ascontiguousarray(aux, dtype=np.float64)
+        if a.ndim != 2 or a.shape[1] != 5:
+            raise ValueError('aux must be [total_pixels][5], got %r' % (a.shape,))
+        batch = getattr(self, '_keep', None)
+        n_pix = batch.total_pixels if isinstance(batch, ChipBatch) else None
+        if n_pix is None and batch is not None and getattr(self, '_n_pix', None) is not None:
+            d = np.asarray(batch[0])
+            n_pix = (d.shape[0] if d.ndim == 2 else 1) * self._n_pix
+        if n_pix is not None and a.shape[0] != n_pix:
+            raise ValueError('aux has %d pixels, the batch %d' % (a.shape[0], n_pix))
+        nr = ctypes.c_int64(0)
+        secs = ctypes.c_double(0.0)
+        L = lib()
+        cap = int(rows_cap) if rows_cap is not None else 2 * a.shape[0] + 64
+        for _ in range(2):
+            out = np.empty((cap, nc), dtype=np.float32)
+            rc = L.ccdgpu_classify_rows(self._ctx, a.ctypes.data, out.ctypes.data, cap, ctypes.byref(nr), ctypes.byref(secs))
+            if rc == 0:
+                break
+            if rows_cap is not None or rc != abi.E_INVAL or nr.value <= cap:
+                self.forest_rows = nr.value
+                _check(rc)
+            cap = nr.value  # more rows than the first guess
+        else:
+            _check(rc)
+        self.forest_seconds = secs.value
+        self.forest_rows = nr.value
+        return out[:nr.value]
 
     def diag_counters(self):
         buf = (ctypes.c_uint64 * 48)()

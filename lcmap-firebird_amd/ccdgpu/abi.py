@@ -11,6 +11,8 @@ import numpy as np
 NBANDS = 7
 MAX_OBS = 4096
 MAX_PEEK = 96
+FOREST_MAX_FEATURES = 64  # CCDGPU_FOREST_MAX_FEATURES
+FOREST_MAX_CLASSES = 32   # CCDGPU_FOREST_MAX_CLASSES
 BANDS = ('blue', 'green', 'red', 'nir', 'swir1', 'swir2', 'thermal')
 PROCEDURES = ('standard_procedure', 'permanent_snow_procedure', 'insufficient_clear_procedure')
 
@@ -135,6 +137,38 @@ class Stats(ctypes.Structure):
                 ('cd_sweeps', ctypes.c_int64), ('flops', ctypes.c_int64), ('bytes', ctypes.c_int64),
                 ('detect_ms_device', _f64), ('pool_reruns', ctypes.c_int64), ('pool_cap', ctypes.c_int64),
                 ('wave_slots', ctypes.c_int64), ('n_cu', ctypes.c_int64)]
+
+
+class Forest(ctypes.Structure):
+    """ccdgpu_forest: a random forest as plain arrays over one node pool (include/ccdgpu.h)."""
+    _fields_ = [('n_trees', _i32), ('n_nodes', _i32), ('n_features', _i32), ('n_classes', _i32),
+                ('root', ctypes.POINTER(_i32)), ('feature', ctypes.POINTER(_i32)),
+                ('threshold', ctypes.POINTER(_f64)), ('left', ctypes.POINTER(_i32)),
+                ('right', ctypes.POINTER(_i32)), ('value', ctypes.POINTER(_f64))]
+
+
+def forest_struct(root, feature, threshold, left, right, value, n_features):
+    """(abi.Forest, the arrays it points into) from array-likes; the sizes come from the arrays
+    (value [n_nodes][n_classes]).  Keep the arrays alive while the struct is in use."""
+    root = np.ascontiguousarray(root, dtype=np.int32).reshape(-1)
+    feature = np.ascontiguousarray(feature, dtype=np.int32).reshape(-1)
+    threshold = np.ascontiguousarray(threshold, dtype=np.float64).reshape(-1)
+    left = np.ascontiguousarray(left, dtype=np.int32).reshape(-1)
+    right = np.ascontiguousarray(right, dtype=np.int32).reshape(-1)
+    value = np.ascontiguousarray(value, dtype=np.float64)
+    n = feature.shape[0]
+    if value.ndim != 2 or value.shape[0] != n or threshold.shape[0] != n or left.shape[0] != n or right.shape[0] != n:
+        raise ValueError('forest arrays disagree: feature %s threshold %s left %s right %s value %s'
+                         % (feature.shape, threshold.shape, left.shape, right.shape, value.shape))
+    f = Forest()
+    f.n_trees, f.n_nodes, f.n_features, f.n_classes = root.shape[0], n, int(n_features), value.shape[1]
+    f.root = root.ctypes.data_as(ctypes.POINTER(_i32))
+    f.feature = feature.ctypes.data_as(ctypes.POINTER(_i32))
+    f.threshold = threshold.ctypes.data_as(ctypes.POINTER(_f64))
+    f.left = left.ctypes.data_as(ctypes.POINTER(_i32))
+    f.right = right.ctypes.data_as(ctypes.POINTER(_i32))
+    f.value = value.ctypes.data_as(ctypes.POINTER(_f64))
+    return f, (root, feature, threshold, left, right, value)
 
 
 # parameter dict keys (pyccd parameters.yaml names) -> Params fields

@@ -126,6 +126,38 @@ int ccdk_default_rows(const int32_t *nseg, int64_t n_pix, const unsigned long lo
 int ccdk_scatter(const ccdgpu_segment *pool, const int32_t *pool_seq, int64_t n_pool,
                  const int64_t *offsets, const int64_t *chip_pix_off, int32_t n_chips, ccdgpu_segment *out,
                  void *stream);
+// random-forest inference (ccd_forest.hip).  Device forest: one relocatable blob per tree, blobs
+// back to back in `pool` -- CcdForestNode[n_t] in breadth-first order (root at 0, the two
+// children of a node adjacent: right = left + 1), then the leaves' class vectors; indices inside
+// a blob are relative to it.  tree_off [n_trees + 1]: byte offsets of the blobs (multiples of
+// 16); chunk_first [n_chunks + 1]: tree ranges walked together -- a range whose bytes fit
+// chunk_cap is copied to LDS first, a tree larger than that is a range of its own, walked from
+// global memory.
+struct __attribute__((aligned(16))) CcdForestNode {
+    double threshold;
+    int32_t feature;  // < 0: leaf
+    int32_t left;     // internal: node index of the left child; leaf: offset of its class vector
+                      // in doubles from the blob's start
+};
+struct CcdForestDev {
+    const unsigned char *pool;
+    const int64_t *tree_off;
+    const int32_t *chunk_first;
+    int32_t n_chunks, n_features, n_classes, max_depth;
+    int32_t threads;    // rows (lanes) per block: ccdk_forest_threads(n_features)
+    int32_t chunk_cap;  // bytes of LDS for a chunk: ccdk_forest_chunk_cap(n_features)
+};
+int32_t ccdk_forest_threads(int32_t n_features);
+int32_t ccdk_forest_chunk_cap(int32_t n_features);
+// x [n_rows][n_features] (device) -> out [n_rows][n_classes]; skip (nullptr, or one byte per row):
+// a flagged row is not walked and gets NaN
+int ccdk_forest_classify(const CcdForestDev *f, const double *x, const unsigned char *skip, int64_t n_rows, float *out,
+                         void *stream);
+// feature matrix of a run's rows (ccdgpu_classify_rows): pixel p's rows row_off[p] .. from its
+// segments seg[seg_off[p] ..] (one default row, flagged in skip, without any) and aux[p][5];
+// n_seg / n_rows bound the segment reads and the row writes
+int ccdk_forest_gather(const ccdgpu_segment *seg, const int64_t *seg_off, const int64_t *row_off, const double *aux,
+                       int64_t n_pix, int64_t n_seg, int64_t n_rows, double *x, unsigned char *skip, void *stream);
 #ifdef __cplusplus
 }
 #endif

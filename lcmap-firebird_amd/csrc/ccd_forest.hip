@@ -1,0 +1,201 @@
+// ccd_forest.hip -- MI355X (gfx950) random-forest inference over segment rows: the `rfrawp`
+// column of the segment table.
+//
+// Reference: ccdc/randomforest.py:25-87 classifies the feature vectors of ccdc/features.py with
+// Spark ML's RandomForestClassificationModel (500 trees) and keeps its rawPrediction -- per row,
+// the sum over the trees, in tree order, of the reached leaf's normalised class distribution --
+// as array<float>.  include/ccdgpu.h states the walk; this kernel reproduces it exactly.
+//
+// One lane per row walks every tree in order and keeps n_classes double accumulators, so the
+// additions of a row happen in tree order whatever the launch shape.  A block's feature vectors
+// sit in LDS as [feature][row] (the feature index of a node is data, so registers cannot hold
+// them; lanes of a wave that test the same feature read consecutive doubles).  The forest streams
+// through the rest of the block's LDS in chunks of whole trees (ccd_device.h, CcdForestDev): the
+// block copies a chunk, every lane walks its trees out of LDS, the next chunk follows.  A tree
+// larger than a chunk is walked from global memory (L2) by the same code.  A node is 16 bytes
+// (threshold, feature, left child; the right child is the next node), read as one b128; the
+// leaves' class vectors follow the nodes of their tree, so a chunk carries them too.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/ccdgpu.h"
+#include "ccd_device.h"
+
+namespace {
+
+constexpr int W = 64;
+constexpr int LDS_BYTES = 160 * 1024;   // per CU, and the most one block may ask for
+constexpr int MIN_CHUNK = 16 * 1024;    // least chunk room a launch shape must leave
+constexpr int GATHER_F = 33;            // ccdc.features.columns()
+
+// bytes of a block's feature vectors: [n_features][threads + 1] doubles (the odd row stride keeps
+// the transposing stores of the load off a single bank), rounded to the chunk's 16-byte alignment
+__host__ __device__ constexpr int feat_bytes(int n_features, int threads) {
+    return (n_features * (threads + 1) * 8 + 15) & ~15;
+}
+
+// One tree for one row: at most max_depth branches (the checked forest's depth; a leaf is
+// always reached within it), then the leaf's class vector added to the accumulators.
+template <int NC>
+__device__ __forceinline__ void walk(const unsigned char *blob, const double *xs_lane, int xs_stride, int max_depth, int nc,
+                                     double (&acc)[NC]) {
+    const CcdForestNode *nodes = reinterpret_cast<const CcdForestNode *>(blob);
+    CcdForestNode nd = nodes[0];
+    for (int d = 0; d < max_depth && nd.feature >= 0; ++d) {
+        const double v = xs_lane[nd.feature * xs_stride];
+        nd = nodes[nd.left + (v <= nd.threshold ? 0 : 1)];  // NaN compares false: right
+    }
+    if (nd.feature >= 0) return;  // (not reached for a checked forest)
+    const double *val = reinterpret_cast<const double *>(blob) + nd.left;
+#pragma unroll
+    for (int k = 0; k < NC; ++k)
+        if (k < nc) acc[k] += val[k];
+}
+
+template <int NC, int T>
+__global__ __launch_bounds__(T) void ccd_forest_classify(CcdForestDev f, const double *__restrict__ x,
+                                                         const unsigned char *__restrict__ skip, int64_t n_rows,
+                                                         float *__restrict__ out) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    constexpr int XS = T + 1;
+    const int nf = f.n_features, nc = f.n_classes;
+    double *xs = reinterpret_cast<double *>(smem);
+    unsigned char *chunk = smem + feat_bytes(nf, T);
+    const int tid = (int)threadIdx.x;
+    const int64_t row0 = (int64_t)blockIdx.x * T;
+    if (row0 >= n_rows) return;
+    const int nrow = n_rows - row0 < T ? (int)(n_rows - row0) : T;
+    // the block's rows, row-major in global memory (coalesced), transposed into LDS
+    const double *xb = x + row0 * nf;
+    for (int i = tid; i < nrow * nf; i += T) {
+        const int r = i / nf, c = i - r * nf;
+        xs[c * XS + r] = xb[i];
+    }
+    const int64_t row = row0 + tid;
+    const bool live = tid < nrow && !(skip && skip[row]);
+    double acc[NC];
+#pragma unroll
+    for (int k = 0; k < NC; ++k) acc[k] = 0.0;
+    const double *xs_lane = xs + tid;
+    for (int c = 0; c < f.n_chunks; ++c) {
+        const int t0 = f.chunk_first[c], t1 = f.chunk_first[c + 1];
+        const int64_t base = f.tree_off[t0];
+        const int64_t bytes = f.tree_off[t1] - base;
+        if (bytes <= (int64_t)f.chunk_cap) {
+            __syncthreads();  // the feature vectors are in place / the previous chunk is done with
+            const uint4 *src = reinterpret_cast<const uint4 *>(f.pool + base);
+            uint4 *dst = reinterpret_cast<uint4 *>(chunk);
+            for (int i = tid; i < (int)(bytes >> 4); i += T) dst[i] = src[i];
+            __syncthreads();
+            if (live)
+                for (int t = t0; t < t1; ++t) walk<NC>(chunk + (f.tree_off[t] - base), xs_lane, XS, f.max_depth, nc, acc);
+        } else {
+            __syncthreads();  // (the feature vectors, when this is the first chunk)
+            if (live)
+                for (int t = t0; t < t1; ++t) walk<NC>(f.pool + f.tree_off[t], xs_lane, XS, f.max_depth, nc, acc);
+        }
+    }
+    if (tid < nrow) {
+        float *o = out + row * nc;
+#pragma unroll
+        for (int k = 0; k < NC; ++k)
+            if (k < nc) o[k] = live ? __double2float_rn(acc[k]) : __uint_as_float(0x7fc00000u);
+    }
+}
+
+// The feature matrix of a run's rows, one wave per pixel, lanes over the elements of its rows:
+// the float32 value the row packer stores (ccd_rows.hip) widened to double, then the pixel's aux
+// values.  n_seg / n_rows bound every read and write.
+__global__ __launch_bounds__(256) void ccd_forest_gather(const ccdgpu_segment *__restrict__ seg, const int64_t *__restrict__ seg_off,
+                                                         const int64_t *__restrict__ row_off, const double *__restrict__ aux,
+                                                         int64_t n_pix, int64_t n_seg, int64_t n_rows, double *__restrict__ x,
+                                                         unsigned char *__restrict__ skip) {
+    const int l = threadIdx.x % W;
+    const int64_t nw = (int64_t)gridDim.x * (blockDim.x / W);
+    for (int64_t p = (int64_t)blockIdx.x * (blockDim.x / W) + threadIdx.x / W; p < n_pix; p += nw) {
+        const int64_t s0 = seg_off[p], ns = seg_off[p + 1] - s0, r0 = row_off[p];
+        const int64_t nr = ns > 0 ? ns : 1;
+        if (s0 < 0 || ns < 0 || s0 + ns > n_seg || r0 < 0 || r0 + nr > n_rows) continue;
+        const double *ax = aux + p * 5;
+        for (int64_t e = l; e < nr * GATHER_F; e += W) {
+            const int64_t j = e / GATHER_F;
+            const int c = (int)(e - j * GATHER_F);
+            double v = 0.0;
+            if (c >= 28) {
+                v = ax[c - 28];
+            } else if (ns > 0) {
+                const ccdgpu_segment &s = seg[s0 + j];
+                v = c < 7 ? s.magnitude[c] : c < 14 ? s.rmse[c - 7] : c < 21 ? s.coef[c - 14][0] : s.intercept[c - 21];
+                v = (double)__double2float_rn(v);
+            }
+            x[(r0 + j) * GATHER_F + c] = v;
+        }
+        for (int64_t j = l; j < nr; j += W) skip[r0 + j] = ns > 0 ? 0 : 1;
+    }
+}
+
+template <int NC, int T>
+int launch(const CcdForestDev &f, const double *x, const unsigned char *skip, int64_t n_rows, float *out, hipStream_t s) {
+    const int lds = feat_bytes(f.n_features, T) + f.chunk_cap;
+    if (lds > LDS_BYTES || f.chunk_cap < 16) return -1;
+    auto k = ccd_forest_classify<NC, T>;
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
+        return -1;
+    const int64_t blocks = (n_rows + T - 1) / T;
+    if (blocks <= 0 || blocks > 0x7fffffff) return -1;
+    hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(T), lds, s, f, x, skip, n_rows, out);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+template <int T>
+int launch_nc(const CcdForestDev &f, const double *x, const unsigned char *skip, int64_t n_rows, float *out, hipStream_t s) {
+    const int nc = f.n_classes;
+    if (nc <= 2) return launch<2, T>(f, x, skip, n_rows, out, s);
+    if (nc <= 4) return launch<4, T>(f, x, skip, n_rows, out, s);
+    if (nc <= 9) return launch<9, T>(f, x, skip, n_rows, out, s);
+    if (nc <= 16) return launch<16, T>(f, x, skip, n_rows, out, s);
+    return launch<32, T>(f, x, skip, n_rows, out, s);
+}
+
+}  // namespace
+
+// Rows per block: 512 where the feature vectors of 512 rows leave a chunk's room in LDS (up to 35
+// features), else 256 (at 33 features the 256-lane shape, two blocks and two half-size chunks per
+// CU, measured 1.9x slower: DESIGN.md 6d).
+extern "C" int32_t ccdk_forest_threads(int32_t n_features) {
+    if (n_features < 1 || n_features > CCDGPU_FOREST_MAX_FEATURES) return 0;
+    return feat_bytes(n_features, 512) + MIN_CHUNK <= LDS_BYTES ? 512 : 256;
+}
+
+// Chunk room: the CU's LDS split among the blocks that fit it (at most 2048 lanes per CU), less
+// the block's feature vectors.
+extern "C" int32_t ccdk_forest_chunk_cap(int32_t n_features) {
+    const int t = ccdk_forest_threads(n_features);
+    if (!t) return 0;
+    const int fb = feat_bytes(n_features, t);
+    int k = LDS_BYTES / (fb + MIN_CHUNK);
+    if (k > 2048 / t) k = 2048 / t;
+    if (k < 1) k = 1;
+    return ((LDS_BYTES / k) & ~15) - fb;
+}
+
+extern "C" int ccdk_forest_classify(const CcdForestDev *f, const double *x, const unsigned char *skip, int64_t n_rows,
+                                    float *out, void *stream) {
+    if (n_rows <= 0) return 0;
+    if (f->n_classes < 1 || f->n_classes > CCDGPU_FOREST_MAX_CLASSES || f->n_features < 1 ||
+        f->n_features > CCDGPU_FOREST_MAX_FEATURES)
+        return -1;
+    if (f->threads == 512) return launch_nc<512>(*f, x, skip, n_rows, out, (hipStream_t)stream);
+    if (f->threads == 256) return launch_nc<256>(*f, x, skip, n_rows, out, (hipStream_t)stream);
+    return -1;
+}
+
+extern "C" int ccdk_forest_gather(const ccdgpu_segment *seg, const int64_t *seg_off, const int64_t *row_off,
+                                  const double *aux, int64_t n_pix, int64_t n_seg, int64_t n_rows, double *x,
+                                  unsigned char *skip, void *stream) {
+    if (n_pix <= 0) return 0;
+    const int64_t b = (n_pix + 3) / 4;
+    hipLaunchKernelGGL(ccd_forest_gather, dim3((unsigned)(b < 1024 ? b : 1024)), dim3(256), 0, (hipStream_t)stream, seg,
+                       seg_off, row_off, aux, n_pix, n_seg, n_rows, x, skip);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}

@@ -266,6 +266,16 @@ struct ccdgpu_ctx {
     std::vector<int32_t> rq_cx, rq_cy;
     DevBuf<int64_t> rowcnt;
     hipEvent_t done_rows = nullptr;
+    // the context's random forest (ccdgpu_forest_set; ccd_forest.hip) and the scratch of a
+    // classification: feature matrix, skip flags, aux values and predictions of a slab of rows
+    bool has_forest = false;
+    CcdForestDev forest{};
+    DevBuf<unsigned char> f_pool, f_skip;
+    DevBuf<int64_t> f_tree_off;
+    DevBuf<int32_t> f_chunk_first;
+    DevBuf<double> f_x, f_aux;
+    DevBuf<float> f_out;
+    hipEvent_t f_ev[2] = {nullptr, nullptr};
     ~ccdgpu_ctx() {
         for (auto *b : {&dates, &sdates, &offsets, &chip_obs_off, &chip_pix_off, &chip_data_off, &row_off, &seg_off1, &b64_off})
             b->release();
@@ -304,6 +314,15 @@ struct ccdgpu_ctx {
         if (done) (void)hipEventDestroy(done);
         if (done_rows) (void)hipEventDestroy(done_rows);
         rowcnt.release();
+        f_pool.release();
+        f_skip.release();
+        f_tree_off.release();
+        f_chunk_first.release();
+        f_x.release();
+        f_aux.release();
+        f_out.release();
+        for (auto &e : f_ev)
+            if (e) (void)hipEventDestroy(e);
         if (stream) (void)hipStreamDestroy(stream);
         release_arg_slot(arg_slot);
     }
@@ -1494,6 +1513,273 @@ void ccdgpu_result_free(ccdgpu_result *r) {
     std::free(r->sorted_dates);
     std::free(r->sort_index);
     std::memset(r, 0, sizeof(*r));
+}
+
+// ---- random-forest classification of segment rows (include/ccdgpu.h; kernels in ccd_forest.hip)
+
+// The checks of ccdgpu_forest_check, and the forest's depth (branches from a root to its deepest
+// leaf).  Children have larger indices than their parents, so one pass in index order carries
+// the depth down from the roots.
+static int forest_validate(const ccdgpu_forest *f, int32_t *max_depth) {
+    if (!f) return fail(CCDGPU_EINVAL, "forest is NULL");
+    if (f->n_trees < 1) return fail(CCDGPU_EINVAL, "forest: n_trees must be >= 1, got " + std::to_string(f->n_trees));
+    if (f->n_nodes < 1) return fail(CCDGPU_EINVAL, "forest: n_nodes must be >= 1, got " + std::to_string(f->n_nodes));
+    if (f->n_features < 1 || f->n_features > CCDGPU_FOREST_MAX_FEATURES)
+        return fail(CCDGPU_EINVAL, "forest: n_features must be in [1, " + std::to_string(CCDGPU_FOREST_MAX_FEATURES) + "], got " +
+                                       std::to_string(f->n_features));
+    if (f->n_classes < 1 || f->n_classes > CCDGPU_FOREST_MAX_CLASSES)
+        return fail(CCDGPU_EINVAL, "forest: n_classes must be in [1, " + std::to_string(CCDGPU_FOREST_MAX_CLASSES) + "], got " +
+                                       std::to_string(f->n_classes));
+    if (!f->root || !f->feature || !f->threshold || !f->left || !f->right || !f->value)
+        return fail(CCDGPU_EINVAL, "forest: NULL array");
+    const int32_t nn = f->n_nodes, nc = f->n_classes;
+    // depth of a node below its root; -1: not reached from any root; parents counted in `seen`
+    std::vector<int32_t> depth((size_t)nn, -1);
+    std::vector<unsigned char> seen((size_t)nn, 0);
+    for (int32_t t = 0; t < f->n_trees; ++t) {
+        const int32_t r = f->root[t];
+        if (r < 0 || r >= nn)
+            return fail(CCDGPU_EINVAL, "forest: root of tree " + std::to_string(t) + " is " + std::to_string(r) +
+                                           ", outside [0, " + std::to_string(nn) + ")");
+        if (seen[r]) return fail(CCDGPU_EINVAL, "forest: node " + std::to_string(r) + " is the root of two trees (shared node)");
+        seen[r] = 1;
+        depth[r] = 0;
+    }
+    int32_t deepest = 0;
+    for (int32_t n = 0; n < nn; ++n) {
+        if (f->feature[n] < 0) {
+            for (int32_t k = 0; k < nc; ++k)
+                if (!std::isfinite(f->value[(size_t)n * nc + k]))
+                    return fail(CCDGPU_EINVAL, "forest: leaf " + std::to_string(n) + " has a non-finite value (class " +
+                                                   std::to_string(k) + ")");
+            if (depth[n] > deepest) deepest = depth[n];
+            continue;
+        }
+        if (f->feature[n] >= f->n_features)
+            return fail(CCDGPU_EINVAL, "forest: node " + std::to_string(n) + " tests feature " + std::to_string(f->feature[n]) +
+                                           " >= n_features " + std::to_string(f->n_features));
+        if (!std::isfinite(f->threshold[n]))
+            return fail(CCDGPU_EINVAL, "forest: node " + std::to_string(n) + " has a non-finite threshold");
+        const int32_t ch[2] = {f->left[n], f->right[n]};
+        for (int32_t side = 0; side < 2; ++side) {
+            const int32_t c = ch[side];
+            const char *name = side ? "right" : "left";
+            if (c < 0 || c >= nn)
+                return fail(CCDGPU_EINVAL, "forest: " + std::string(name) + " child of node " + std::to_string(n) + " is " +
+                                               std::to_string(c) + ", outside [0, " + std::to_string(nn) + ")");
+            if (c <= n)
+                return fail(CCDGPU_EINVAL, "forest: " + std::string(name) + " child of node " + std::to_string(n) + " is " +
+                                               std::to_string(c) + ", not greater than its parent's index");
+            if (seen[c]) return fail(CCDGPU_EINVAL, "forest: node " + std::to_string(c) + " has two parents (shared node)");
+            seen[c] = 1;
+            if (depth[n] >= 0) depth[c] = depth[n] + 1;
+        }
+    }
+    if (max_depth) *max_depth = deepest;
+    return 0;
+}
+
+int ccdgpu_forest_check(const ccdgpu_forest *f) { return forest_validate(f, nullptr); }
+
+int ccdgpu_forest_depth(const ccdgpu_forest *f, int32_t *max_depth) {
+    if (!max_depth) return fail(CCDGPU_EINVAL, "NULL argument");
+    *max_depth = 0;
+    return forest_validate(f, max_depth);
+}
+
+int ccdgpu_forest_clear(ccdgpu_ctx *c) {
+    if (!c) return fail(CCDGPU_EINVAL, "NULL ctx");
+    (void)hipSetDevice(c->device);
+    c->has_forest = false;
+    c->forest = CcdForestDev{};
+    c->f_pool.release();
+    c->f_tree_off.release();
+    c->f_chunk_first.release();
+    return 0;
+}
+
+// The device form of a checked forest (ccd_device.h): per tree one blob, nodes breadth-first so
+// that the children of a node are adjacent, the leaves' class vectors behind the nodes; then the
+// chunks: runs of whole trees that fit `cap` bytes, a larger tree alone.
+static int forest_build(const ccdgpu_forest *f, int32_t cap, std::vector<unsigned char> &pool, std::vector<int64_t> &tree_off,
+                        std::vector<int32_t> &chunk_first) {
+    const int32_t nt = f->n_trees, nc = f->n_classes;
+    tree_off.assign((size_t)nt + 1, 0);
+    pool.clear();
+    std::vector<int32_t> order;
+    for (int32_t t = 0; t < nt; ++t) {
+        order.assign(1, f->root[t]);
+        size_t leaves = 0;
+        for (size_t i = 0; i < order.size(); ++i) {
+            const int32_t n = order[i];
+            if (f->feature[n] < 0) {
+                ++leaves;
+            } else {
+                order.push_back(f->left[n]);
+                order.push_back(f->right[n]);
+            }
+        }
+        const size_t n_t = order.size();
+        const size_t bytes = (n_t * sizeof(CcdForestNode) + leaves * nc * sizeof(double) + 15) & ~(size_t)15;
+        if (bytes / 8 >= (size_t)INT32_MAX) return fail(CCDGPU_EINVAL, "forest: tree " + std::to_string(t) + " is too large");
+        const size_t at = pool.size();
+        pool.resize(at + bytes, 0);
+        CcdForestNode *nodes = reinterpret_cast<CcdForestNode *>(pool.data() + at);
+        double *vals = reinterpret_cast<double *>(pool.data() + at);
+        size_t next = 1, leaf = 0;
+        for (size_t i = 0; i < n_t; ++i) {
+            const int32_t n = order[i];
+            if (f->feature[n] < 0) {
+                const size_t v = n_t * sizeof(CcdForestNode) / sizeof(double) + leaf * nc;
+                nodes[i].threshold = 0.0;
+                nodes[i].feature = -1;
+                nodes[i].left = (int32_t)v;
+                std::memcpy(vals + v, f->value + (size_t)n * nc, sizeof(double) * nc);
+                ++leaf;
+            } else {
+                nodes[i].threshold = f->threshold[n];
+                nodes[i].feature = f->feature[n];
+                nodes[i].left = (int32_t)next;
+                next += 2;
+            }
+        }
+        tree_off[t + 1] = (int64_t)pool.size();
+    }
+    chunk_first.assign(1, 0);
+    for (int32_t t = 0; t < nt;) {
+        int32_t e = t + 1;
+        if (tree_off[e] - tree_off[t] <= cap)
+            while (e < nt && tree_off[e + 1] - tree_off[t] <= cap) ++e;
+        chunk_first.push_back(e);
+        t = e;
+    }
+    return 0;
+}
+
+int ccdgpu_forest_set(ccdgpu_ctx *c, const ccdgpu_forest *f) {
+    if (!c) return fail(CCDGPU_EINVAL, "NULL ctx");
+    int32_t max_depth = 0;
+    int rc = forest_validate(f, &max_depth);
+    if (rc) return rc;
+    const int32_t nc = f->n_classes;
+    const int32_t cap = ccdk_forest_chunk_cap(f->n_features);
+    std::vector<unsigned char> pool;
+    std::vector<int64_t> tree_off;
+    std::vector<int32_t> chunk_first;
+    if ((rc = forest_build(f, cap, pool, tree_off, chunk_first))) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->aux));
+    c->has_forest = false;
+    if ((rc = c->f_pool.ensure(pool.size())) || (rc = c->f_tree_off.ensure(tree_off.size())) ||
+        (rc = c->f_chunk_first.ensure(chunk_first.size())))
+        return rc;
+    HIPCHK(hipMemcpy(c->f_pool.p, pool.data(), pool.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(c->f_tree_off.p, tree_off.data(), sizeof(int64_t) * tree_off.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(c->f_chunk_first.p, chunk_first.data(), sizeof(int32_t) * chunk_first.size(), hipMemcpyHostToDevice));
+    for (auto &e : c->f_ev)
+        if (!e) HIPCHK(hipEventCreate(&e));
+    c->forest.pool = c->f_pool.p;
+    c->forest.tree_off = c->f_tree_off.p;
+    c->forest.chunk_first = c->f_chunk_first.p;
+    c->forest.n_chunks = (int32_t)chunk_first.size() - 1;
+    c->forest.n_features = f->n_features;
+    c->forest.n_classes = nc;
+    c->forest.max_depth = max_depth;
+    c->forest.threads = ccdk_forest_threads(f->n_features);
+    c->forest.chunk_cap = cap;
+    c->has_forest = true;
+    return 0;
+}
+
+// rows a classification keeps on the device at a time (the host-matrix path goes slab by slab;
+// a row's result does not depend on its slab)
+static const int64_t FOREST_SLAB = (int64_t)1 << 20;
+
+int ccdgpu_classify(ccdgpu_ctx *c, const double *features, int64_t n_rows, float *rfrawp, double *kernel_seconds) {
+    if (kernel_seconds) *kernel_seconds = 0.0;
+    if (!c) return fail(CCDGPU_EINVAL, "NULL ctx");
+    if (!c->has_forest) return fail(CCDGPU_EINVAL, "no forest set (ccdgpu_forest_set)");
+    if (c->pending) return fail(CCDGPU_EINVAL, "a detection begun with ccdgpu_run_slot_begin is not finished");
+    if (n_rows < 0) return fail(CCDGPU_EINVAL, "n_rows must be >= 0");
+    if (n_rows == 0) return 0;
+    if (!features || !rfrawp) return fail(CCDGPU_EINVAL, "NULL argument");
+    HIPCHK(hipSetDevice(c->device));
+    const int64_t nf = c->forest.n_features, nc = c->forest.n_classes;
+    const int64_t slab = std::min(n_rows, FOREST_SLAB);
+    int rc;
+    if ((rc = c->f_x.ensure((size_t)(slab * nf))) || (rc = c->f_out.ensure((size_t)(slab * nc)))) return rc;
+    hipStream_t ax = c->aux;
+    double secs = 0.0;
+    for (int64_t r0 = 0; r0 < n_rows; r0 += slab) {
+        const int64_t n = std::min(slab, n_rows - r0);
+        HIPCHK(hipMemcpyAsync(c->f_x.p, features + r0 * nf, sizeof(double) * (size_t)(n * nf), hipMemcpyHostToDevice, ax));
+        HIPCHK(hipEventRecord(c->f_ev[0], ax));
+        if (ccdk_forest_classify(&c->forest, c->f_x.p, nullptr, n, c->f_out.p, ax)) {
+            (void)hipStreamSynchronize(ax);
+            return fail(CCDGPU_EHIP, "forest kernel launch failed");
+        }
+        HIPCHK(hipEventRecord(c->f_ev[1], ax));
+        HIPCHK(hipMemcpyAsync(rfrawp + r0 * nc, c->f_out.p, sizeof(float) * (size_t)(n * nc), hipMemcpyDeviceToHost, ax));
+        HIPCHK(hipStreamSynchronize(ax));
+        float ms = 0.f;
+        (void)hipEventElapsedTime(&ms, c->f_ev[0], c->f_ev[1]);
+        secs += ms * 1e-3;
+    }
+    if (kernel_seconds) *kernel_seconds = secs;
+    return 0;
+}
+
+int ccdgpu_classify_rows(ccdgpu_ctx *c, const double *aux, float *rfrawp, int64_t rows_cap, int64_t *n_rows,
+                         double *kernel_seconds) {
+    if (kernel_seconds) *kernel_seconds = 0.0;
+    if (!n_rows) return fail(CCDGPU_EINVAL, "NULL argument");
+    *n_rows = 0;
+    if (!c) return fail(CCDGPU_EINVAL, "NULL ctx");
+    if (c->pending) return fail(CCDGPU_EINVAL, "a detection begun with ccdgpu_run_slot_begin is not finished");
+    if (!c->ran || c->shape.n_chips() <= 0) return fail(CCDGPU_EINVAL, "no completed run to classify");
+    // the rows of the run, as ccdgpu_fetch_batch_rows_into counts them: max(1, segments) per pixel
+    const int64_t np = c->shape.total_pix();
+    if ((int64_t)c->h_offsets.size() < np + 1) return fail(CCDGPU_EINVAL, "no completed run to classify");
+    int64_t nr = 0;
+    for (int64_t i = 0; i < np; ++i) nr += std::max<int64_t>(1, c->h_offsets[i + 1] - c->h_offsets[i]);
+    *n_rows = nr;
+    if (!c->has_forest) return fail(CCDGPU_EINVAL, "no forest set (ccdgpu_forest_set)");
+    if (c->forest.n_features != 33)
+        return fail(CCDGPU_EINVAL, "classify_rows needs a forest of 33 features (ccdc.features.columns()), this one has " +
+                                       std::to_string(c->forest.n_features));
+    if (rows_cap < nr)
+        return fail(CCDGPU_EINVAL, "classify_rows: buffer too small (need " + std::to_string(nr) + " rows)");
+    if (!aux || !rfrawp) return fail(CCDGPU_EINVAL, "NULL argument");
+    HIPCHK(hipSetDevice(c->device));
+    const int64_t nc = c->forest.n_classes;
+    const int64_t s0 = c->h_offsets[0], n_seg = c->h_offsets[np] - s0;
+    int rc;
+    if ((rc = c->row_off.ensure(np + 1)) || (rc = c->seg_off1.ensure(np + 1)) || (rc = c->f_aux.ensure((size_t)np * 5)) ||
+        (rc = c->f_x.ensure((size_t)nr * 33)) || (rc = c->f_skip.ensure((size_t)nr)) || (rc = c->f_out.ensure((size_t)(nr * nc))))
+        return rc;
+    const size_t ob = sizeof(int64_t) * (size_t)(np + 1);
+    if ((rc = c->h_fo.ensure(2 * ob))) return rc;
+    int64_t *soff = reinterpret_cast<int64_t *>(c->h_fo.p), *roff = soff + (np + 1);
+    roff[0] = 0;
+    for (int64_t i = 0; i <= np; ++i) soff[i] = c->h_offsets[i] - s0;
+    for (int64_t i = 0; i < np; ++i) roff[i + 1] = roff[i] + std::max<int64_t>(1, soff[i + 1] - soff[i]);
+    hipStream_t ax = c->aux;
+    HIPCHK(hipMemcpyAsync(c->seg_off1.p, soff, ob, hipMemcpyHostToDevice, ax));
+    HIPCHK(hipMemcpyAsync(c->row_off.p, roff, ob, hipMemcpyHostToDevice, ax));
+    HIPCHK(hipMemcpyAsync(c->f_aux.p, aux, sizeof(double) * (size_t)np * 5, hipMemcpyHostToDevice, ax));
+    HIPCHK(hipEventRecord(c->f_ev[0], ax));
+    if (ccdk_forest_gather(c->csr.p + s0, c->seg_off1.p, c->row_off.p, c->f_aux.p, np, n_seg, nr, c->f_x.p, c->f_skip.p, ax) ||
+        ccdk_forest_classify(&c->forest, c->f_x.p, c->f_skip.p, nr, c->f_out.p, ax)) {
+        (void)hipStreamSynchronize(ax);
+        return fail(CCDGPU_EHIP, "forest kernel launch failed");
+    }
+    HIPCHK(hipEventRecord(c->f_ev[1], ax));
+    HIPCHK(hipMemcpyAsync(rfrawp, c->f_out.p, sizeof(float) * (size_t)(nr * nc), hipMemcpyDeviceToHost, ax));
+    HIPCHK(hipStreamSynchronize(ax));
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, c->f_ev[0], c->f_ev[1]);
+    if (kernel_seconds) *kernel_seconds = ms * 1e-3;
+    return 0;
 }
 
 }  // extern "C"
