@@ -269,18 +269,54 @@ int ccdgpu_run_slot_end_rows(ccdgpu_ctx *ctx, double *kernel_seconds, int64_t *n
  *           observation); int16 bands[7][band_stride] (kept observations, pixel-major) -- each
  *           part 16-byte aligned
  *   mode 0: uint16 qa[n_pix][n_obs]; int16 spectra[7][n_pix][n_obs].
+ *   mode 2 (bit-packed band runs; only from the _flags encoder with CCDGPU_ENC_PACK): the header
+ *           as in mode 1 with mode = 2, band_stride = 0, int64 code_words at byte 88 and int64
+ *           exc_total at byte 96; then, each part 16-byte aligned:
+ *             uint32 kept_off[n_pix + 1]; uint8 qa4[n_pix][(n_obs + 1) / 2]      (as in mode 1)
+ *             run[n_pix][7], 16 bytes each: int16 base; uint16 w; uint32 code_word; uint32 exc_off;
+ *                                           uint32 n_exc
+ *             uint32 codes[code_words + 1]  (the last word is a zero pad: a decoder may always
+ *                                           read word i + 1)
+ *             int16 exc[exc_total]
+ *           For pixel p and band b the kept values in observation order are v_0 .. v_{k-1},
+ *           k = kept_off[p + 1] - kept_off[p].  base = min v (0 when k = 0); r_i = v_i - base in
+ *           0 .. 65535 (32-bit arithmetic).  The width w is 0 .. 16:
+ *             w = 16      the code is r_i, no escapes;
+ *             w = 1 .. 15 the code is r_i if r_i < 2^w - 1, else the escape 2^w - 1 and the raw v_i
+ *                         is appended to the run's exception list (in order);
+ *             w = 0       only when every r_i is 0: no bits stored.
+ *           The encoder's w is canonical: the one that minimises w k + 16 e(w), e(w) = the number
+ *           of r_i >= 2^w - 1 for w = 1 .. 15, e(16) = 0, w = 0 eligible only with all values
+ *           equal; ties go to the smallest w.  The run's codes take ceil(k w / 32) words from
+ *           codes[code_word]: bit j of the run is bit j & 31 of word j >> 5, unused top bits of the
+ *           last word 0.  Runs lie back to back in (pixel, band) order, so code_word and exc_off
+ *           are prefix sums with totals code_words and exc_total, and the bytes are a pure function
+ *           of the input (any thread count, scalar or vector encoder).  A packed batch holds mode
+ *           2 and mode 0 (raw fallback) sections only.
  * ccdgpu_stage_slot_encoded uploads such a batch (and the dates) into a slot and decodes it on the
  * device, on the copy stream, into exactly the buffers ccdgpu_stage_slot_chips would fill; run it
- * with ccdgpu_run_slot.  ccdgpu_encode_vector_path: 1 if the encoder uses AVX-512 VBMI2. */
+ * with ccdgpu_run_slot.  ccdgpu_encode_vector_path: 1 if the encoder uses AVX-512 VBMI2.
+ * The _flags forms take CCDGPU_ENC_* flags; flags = 0 is the plain form (same bytes, same bound). */
+#define CCDGPU_ENC_PACK 1u   /* encodable chips as mode 2 sections instead of mode 1 */
 int64_t ccdgpu_encoded_bound(int32_t n_chips, const int32_t *n_pix, const int32_t *n_obs);
 int64_t ccdgpu_encode_chips(int32_t n_chips, const int32_t *n_pix, const int32_t *n_obs, const int16_t *const *spectra,
                             const uint16_t *const *qa, uint8_t *out, int64_t out_cap, int32_t threads,
                             uint16_t drop_bits, uint16_t strict_bits);
+int64_t ccdgpu_encoded_bound_flags(int32_t n_chips, const int32_t *n_pix, const int32_t *n_obs, uint32_t flags);
+int64_t ccdgpu_encode_chips_flags(int32_t n_chips, const int32_t *n_pix, const int32_t *n_obs,
+                                  const int16_t *const *spectra, const uint16_t *const *qa, uint8_t *out,
+                                  int64_t out_cap, int32_t threads, uint16_t drop_bits, uint16_t strict_bits,
+                                  uint32_t flags);
 int32_t ccdgpu_encode_vector_path(void);
 /* The checks ccdgpu_stage_slot_encoded makes before an encoded batch is uploaded (no device
  * needed): the chip table, every section's header against the chip's shape, every section long
  * enough for its mode's layout, and each encoded section's kept-offset table a run per pixel
- * ending at its kept count.  0, or CCDGPU_EINVAL with the reason in ccdgpu_last_error(). */
+ * ending at its kept count.  For a mode 2 section also: every run's w <= 16, its code_word and
+ * exc_off equal to the prefix sums of ceil(k w / 32) and n_exc over the runs before it, n_exc <= k,
+ * the totals equal to the header's code_words and exc_total, and the section long enough for all
+ * five parts including the pad word -- a batch that passes is safe to decode whatever its code bits
+ * say; modes 1 and 2 do not share a batch.  0, or CCDGPU_EINVAL with the reason in
+ * ccdgpu_last_error(). */
 int ccdgpu_encoded_check(int32_t n_chips, const int32_t *n_pix, const int32_t *n_obs, const uint8_t *enc,
                          int64_t enc_bytes);
 int ccdgpu_stage_slot_encoded(ccdgpu_ctx *ctx, int32_t slot, const ccdgpu_params *params, int32_t n_chips,

@@ -256,12 +256,16 @@ class EncodingSource(object):
     of the raw bytes, 'lossless' ~82 %: the PCIe link bounds the tile.  The encode
     is the pass every fetched chip needs anyway to reach pinned memory: a source with a
     ``views(positions)`` method hands over its own arrays (no copy before the encode); otherwise
-    its batch is encoded and released at once.  ``bytes_raw`` / ``bytes_sent`` count the traffic."""
+    its batch is encoded and released at once.  ``bytes_raw`` / ``bytes_sent`` count the traffic.
+    ``pack=True``: the kept band values travel bit-packed (the encoding's mode 2: per (pixel, band)
+    a base, a bit width and an exception list), decoded to the same device inputs by a kernel of
+    its own on the copy stream; fewer bytes for more encoder work."""
 
-    def __init__(self, source, threads=4, pinned=None, drop='unread', params=None):
+    def __init__(self, source, threads=4, pinned=None, drop='unread', params=None, pack=False):
         import ccdgpu
         self.source = source
         self.threads = int(threads)
+        self.pack = bool(pack)
         if drop == 'unread':
             self.drop_bits, self.strict_bits = ccdgpu.unread_drop_bits(params)
         elif drop == 'lossless':
@@ -297,7 +301,7 @@ class EncodingSource(object):
                     break
         if st is None:
             st = (need, self._storage(need))
-        b = ccdgpu.EncodedBatch(n_pix, n_obs, storage=st[1])
+        b = ccdgpu.EncodedBatch(n_pix, n_obs, storage=st[1], pack=self.pack)
         b._enc_storage = st
         b.fill(chips, self.threads, self.drop_bits, self.strict_bits)
         if raw is not None:
@@ -314,12 +318,12 @@ class EncodingSource(object):
         import ccdgpu
         if self.pinned is not False:
             try:
-                return ccdgpu.encode_storage(*need, pinned=True)
+                return ccdgpu.encode_storage(*need, pinned=True, pack=self.pack)
             except ccdgpu.CcdGpuError:
                 if self.pinned:
                     raise
                 self.pinned = False  # no device runtime here: pageable buffers (synchronous uploads)
-        return ccdgpu.encode_storage(*need, pinned=False)
+        return ccdgpu.encode_storage(*need, pinned=False, pack=self.pack)
 
     def release(self, batch):
         st = getattr(batch, '_enc_storage', None)
@@ -526,7 +530,7 @@ def _worker(ctx, queue, source, xys, batch_chips, params, width, sink, stats, er
 
 def detect_tile(xys, source, queue, device=0, contexts=4, batch_chips=6, params=None, width=100,
                 sink=None, context_factory=None, upload_depth=2, tail_chips=None, bind_numa=True, encode=True,
-                encode_threads=3, copy_cus=8):
+                encode_threads=3, copy_cus=8, encode_pack=False):
     """Change detection of the tile chips at ``xys`` (list of (cx, cy), tile order) on one GPU.
 
     ``source(positions) -> ccdgpu.ChipBatch`` supplies the ARD of the chips at those tile
@@ -542,7 +546,8 @@ def detect_tile(xys, source, queue, device=0, contexts=4, batch_chips=6, params=
     full batches per context of this process).  ``encode``: upload every batch in the transport
     encoding (EncodingSource, ``encode_threads`` host threads per fetch; True = its 'unread'
     setting, 'lossless' = lossless) instead of raw -- ``source`` may then also be an
-    EncodingSource already (its counters are reported).  ``copy_cus``: CUs each context reserves
+    EncodingSource already (its counters are reported).  ``encode_pack``: the EncodingSource built
+    here bit-packs the band runs (its ``pack``).  ``copy_cus``: CUs each context reserves
     for its upload (decode kernel, blits) so other contexts' persistent detection waves cannot
     starve it (ccdgpu_init_copy_cus; 0 = none; not used with a ``context_factory``)."""
     from ccdgpu import UPLOAD_SLOTS
@@ -559,7 +564,7 @@ def detect_tile(xys, source, queue, device=0, contexts=4, batch_chips=6, params=
             return ccdgpu.Context(dev, copy_cus=copy_cus)
     if encode and not isinstance(source, EncodingSource):
         source = EncodingSource(source, threads=encode_threads, drop='lossless' if encode == 'lossless' else 'unread',
-                                params=params)
+                                params=params, pack=encode_pack)
     sink = sink if sink is not None else SummarySink()
     # per-phase host seconds summed over the workers: source (ARD fetch), stage (upload call),
     # device (run_slot: waits for the upload, detects), fetch (row packing + D2H), sink
@@ -638,7 +643,7 @@ class TileError(RuntimeError):
 
 def changedetection(tile, source, device=None, contexts=4, batch_chips=6, number=None, params=None,
                     sink=None, width=100, context_factory=None, ctx=None, upload_depth=2, tail_chips=None,
-                    bind_numa=True, encode=True, encode_threads=3, copy_cus=8):
+                    bind_numa=True, encode=True, encode_threads=3, copy_cus=8, encode_pack=False):
     """Change detection for a tile on every GPU of the job (reference core.changedetection,
     ccdc/core.py:78-123).
 
@@ -681,7 +686,8 @@ def changedetection(tile, source, device=None, contexts=4, batch_chips=6, number
         sink, stats = detect_tile(xys, source, queue, device=device, contexts=contexts, batch_chips=batch_chips,
                                   params=params, width=width, sink=sink, context_factory=context_factory,
                                   upload_depth=upload_depth, tail_chips=tail_chips, bind_numa=bind_numa,
-                                  encode=encode, encode_threads=encode_threads, copy_cus=copy_cus)
+                                  encode=encode, encode_threads=encode_threads, copy_cus=copy_cus,
+                                  encode_pack=encode_pack)
     except Exception as e:
         if not (dist_on and dist.get_world_size() > 1):
             raise

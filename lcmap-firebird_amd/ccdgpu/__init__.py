@@ -70,6 +70,12 @@ def _declare(L):
         L.ccdgpu_stage_slot_encoded.argtypes = [c.c_void_p, c.c_int32, c.c_void_p, c.c_int32, c.c_void_p, c.c_void_p,
                                                 c.c_void_p, c.c_void_p, c.c_int64]
         L.ccdgpu_stage_slot_encoded.restype = c.c_int
+    if hasattr(L, 'ccdgpu_encode_chips_flags'):  # (the bit-packed mode 2: pack=True needs it)
+        L.ccdgpu_encoded_bound_flags.argtypes = [c.c_int32, c.c_void_p, c.c_void_p, c.c_uint32]
+        L.ccdgpu_encoded_bound_flags.restype = c.c_int64
+        L.ccdgpu_encode_chips_flags.argtypes = [c.c_int32, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p,
+                                                c.c_int64, c.c_int32, c.c_uint16, c.c_uint16, c.c_uint32]
+        L.ccdgpu_encode_chips_flags.restype = c.c_int64
     if hasattr(L, 'ccdgpu_encoded_check'):
         L.ccdgpu_encoded_check.argtypes = [c.c_int32, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64]
         L.ccdgpu_encoded_check.restype = c.c_int
@@ -136,7 +142,7 @@ EXPORTS = ('ccdgpu_version', 'ccdgpu_last_error', 'ccdgpu_params_default', 'ccdg
            'ccdgpu_run_slot_begin', 'ccdgpu_run_query', 'ccdgpu_run_slot_end', 'ccdgpu_fetch_batch_rows_into',
            'ccdgpu_run_slot_begin_rows', 'ccdgpu_run_slot_end_rows', 'ccdgpu_encoded_check',
            'ccdgpu_forest_check', 'ccdgpu_forest_depth', 'ccdgpu_forest_set', 'ccdgpu_forest_clear',
-           'ccdgpu_classify', 'ccdgpu_classify_rows')
+           'ccdgpu_classify', 'ccdgpu_classify_rows', 'ccdgpu_encoded_bound_flags', 'ccdgpu_encode_chips_flags')
 
 
 def lib():
@@ -268,9 +274,14 @@ class EncodedBatch(ChipBatch):
     (dates, None, None) -- the pixel data exist only in encoded form.
 
         e = EncodedBatch.encode([(d0, s0, q0), (d1, s1, q1)], storage=encode_storage(...))
+
+    ``pack=True`` (here, in ``fill`` / ``encode`` and in ``encode_storage``): the encodable chips'
+    band runs travel bit-packed (mode 2 sections: per (pixel, band) a base, a bit width and an
+    exception list) instead of as int16 columns -- fewer bytes, the same device inputs; the batch
+    and its storage are then sized by the packed bound.
     """
 
-    def __init__(self, n_pix, n_obs, storage=None, pinned=True):
+    def __init__(self, n_pix, n_obs, storage=None, pinned=True, pack=False):
         self.n_pix = np.ascontiguousarray(n_pix, dtype=np.int32).reshape(-1)
         self.n_obs = np.ascontiguousarray(n_obs, dtype=np.int32).reshape(-1)
         if self.n_pix.shape != self.n_obs.shape or self.n_pix.size == 0:
@@ -278,7 +289,8 @@ class EncodedBatch(ChipBatch):
         self.obs_off = np.concatenate([[0], np.cumsum(self.n_obs, dtype=np.int64)])
         self.pix_off = np.concatenate([[0], np.cumsum(self.n_pix, dtype=np.int64)])
         self.data_off = np.concatenate([[0], np.cumsum(self.n_pix.astype(np.int64) * self.n_obs)])
-        bound = int(lib().ccdgpu_encoded_bound(self.n_chips, self.n_pix.ctypes.data, self.n_obs.ctypes.data))
+        self.pack = bool(pack)
+        bound = _encoded_bound(self.n_chips, self.n_pix, self.n_obs, self.pack)
         nd = int(self.obs_off[-1])
         self.storage = storage
         if storage is not None:
@@ -304,13 +316,15 @@ class EncodedBatch(ChipBatch):
     def set_chip(self, c, dates, spectra, qa):
         raise TypeError('EncodedBatch holds encoded chips: build it with EncodedBatch.encode')
 
-    def fill(self, chips, threads=4, drop_bits=1, strict_bits=1):
+    def fill(self, chips, threads=4, drop_bits=1, strict_bits=1, pack=None):
         """Encode chips [(dates [n], spectra [7][n_pix][n] int16, qa [n_pix][n] uint16), ...]
         (any C-contiguous arrays: pinned batch views, or a source's own arrays -- nothing else is
         copied) into this batch; returns the encoded bytes.  ``drop_bits`` / ``strict_bits``:
         QA bits whose observations send no band values / must hold -9999 (include/ccdgpu.h; the
         default, the fill bit for both, is lossless; ``unread_drop_bits(params)`` gives the bits of
-        observations the detection never reads)."""
+        observations the detection never reads).  ``pack`` (default: the batch's own setting)
+        selects the bit-packed mode 2; a batch built without it may be too small for it."""
+        pack = self.pack if pack is None else bool(pack)
         chips = list(chips)
         if len(chips) != self.n_chips:
             raise ValueError('%d chips for a batch of %d' % (len(chips), self.n_chips))
@@ -328,19 +342,23 @@ class EncodedBatch(ChipBatch):
             self.dates[o:o + d.shape[0]] = d
             sp[i], qp[i] = s.ctypes.data, q.ctypes.data
             keep.append((s, q))
-        n = int(lib().ccdgpu_encode_chips(self.n_chips, self.n_pix.ctypes.data, self.n_obs.ctypes.data,
-                                          ctypes.cast(sp, ctypes.c_void_p), ctypes.cast(qp, ctypes.c_void_p),
-                                          self.buf.ctypes.data, self.buf.size, int(threads), int(drop_bits),
-                                          int(strict_bits)))
+        args = (self.n_chips, self.n_pix.ctypes.data, self.n_obs.ctypes.data, ctypes.cast(sp, ctypes.c_void_p),
+                ctypes.cast(qp, ctypes.c_void_p), self.buf.ctypes.data, self.buf.size, int(threads), int(drop_bits),
+                int(strict_bits))
+        if pack:
+            n = int(lib().ccdgpu_encode_chips_flags(*(args + (abi.ENC_PACK,))))
+        else:
+            n = int(lib().ccdgpu_encode_chips(*args))
         if n < 0:
             raise ValueError('ccdgpu_encode_chips failed (%d)' % n)
         self.nbytes_encoded = n
         return n
 
     @classmethod
-    def encode(cls, chips, threads=4, storage=None, pinned=True, drop_bits=1, strict_bits=1):
+    def encode(cls, chips, threads=4, storage=None, pinned=True, drop_bits=1, strict_bits=1, pack=False):
         chips = list(chips)
-        b = cls([c[2].shape[0] for c in chips], [c[0].shape[0] for c in chips], storage=storage, pinned=pinned)
+        b = cls([c[2].shape[0] for c in chips], [c[0].shape[0] for c in chips], storage=storage, pinned=pinned,
+                pack=pack)
         b.fill(chips, threads, drop_bits, strict_bits)
         return b
 
@@ -351,18 +369,25 @@ class EncodedBatch(ChipBatch):
                                           self.buf.ctypes.data, int(self.nbytes_encoded)))
 
     def chip_modes(self):
-        """Per chip: 1 if encoded, 0 if sent raw (from the section headers)."""
+        """Per chip: 1 if encoded, 2 if encoded with bit-packed band runs, 0 if sent raw (from
+        the section headers)."""
         off = self.buf[8:8 * (self.n_chips + 2)].view(np.int64)
         return [int(self.buf[int(o):int(o) + 4].view(np.int32)[0]) for o in off[:self.n_chips]]
 
 
-def encode_storage(max_chips, max_pix, max_obs, pinned=True):
+def _encoded_bound(n_chips, n_pix, n_obs, pack):
+    if pack:
+        return int(lib().ccdgpu_encoded_bound_flags(n_chips, n_pix.ctypes.data, n_obs.ctypes.data, abi.ENC_PACK))
+    return int(lib().ccdgpu_encoded_bound(n_chips, n_pix.ctypes.data, n_obs.ctypes.data))
+
+
+def encode_storage(max_chips, max_pix, max_obs, pinned=True, pack=False):
     """Reusable buffers for EncodedBatch(..., storage=...): room for ``max_chips`` chips of up to
-    ``max_pix`` pixels x ``max_obs`` observations."""
+    ``max_pix`` pixels x ``max_obs`` observations (``pack``: of the bit-packed mode 2)."""
     n = int(max_chips)
     np_ = np.full(n, int(max_pix), dtype=np.int32)
     no = np.full(n, int(max_obs), dtype=np.int32)
-    bound = int(lib().ccdgpu_encoded_bound(n, np_.ctypes.data, no.ctypes.data))
+    bound = _encoded_bound(n, np_, no, pack)
     alloc = pinned_empty if pinned else np.empty
     return alloc((n * int(max_obs),), np.int64), alloc((bound,), np.uint8)
 

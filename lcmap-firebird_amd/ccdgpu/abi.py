@@ -13,6 +13,7 @@ MAX_OBS = 4096
 MAX_PEEK = 96
 FOREST_MAX_FEATURES = 64  # CCDGPU_FOREST_MAX_FEATURES
 FOREST_MAX_CLASSES = 32   # CCDGPU_FOREST_MAX_CLASSES
+ENC_PACK = 1              # CCDGPU_ENC_PACK: flag of ccdgpu_encode_chips_flags / ccdgpu_encoded_bound_flags
 BANDS = ('blue', 'green', 'red', 'nir', 'swir1', 'swir2', 'thermal')
 PROCEDURES = ('standard_procedure', 'permanent_snow_procedure', 'insufficient_clear_procedure')
 

@@ -97,6 +97,8 @@ int ccdk_unpack_b64(const unsigned char *text, int64_t text_bytes, const int64_t
                     void *stream);
 // transport-encoded batch (ccd_encode.c) -> spectra / qa in the standard layout (ccd_pack.hip)
 int ccdk_decode_enc(const unsigned char *enc, int64_t total_pix, int16_t *spectra, uint16_t *qa, void *stream);
+// the same for a batch with bit-packed (mode 2) sections (ccd_decode_pack)
+int ccdk_decode_pack(const unsigned char *enc, int64_t total_pix, int16_t *spectra, uint16_t *qa, void *stream);
 // detection results -> segment / pixel table rows (ccd_rows.hip)
 // (skip: nullptr, or a device flag that makes the launch write nothing; seg_cap / rows_cap bound
 // the segment reads and row writes)

@@ -17,6 +17,9 @@
  * The device decoder (ccd_decode_enc in ccd_pack.hip) rebuilds the standard band-major
  * [7][n_pix][n_obs] spectra and [n_pix][n_obs] QA of every chip (tests/test_encode.py: round
  * trips against a numpy decoder).  Layout: include/ccdgpu.h.
+ *   - with CCDGPU_ENC_PACK (ccdgpu_encode_chips_flags) the kept band values of each (pixel, band)
+ *     travel as a base, a bit width and bit-packed residuals with an exception list (mode 2,
+ *     decoded by ccd_decode_pack; tests/test_encode_pack.py) instead of as int16 columns.
  *
  * The encode replaces the copy into pinned memory that every upload from a fetched (pageable)
  * chip needs anyway; it runs one pass over the QA words (counts, palette, fill check) and one
@@ -46,15 +49,28 @@ static size_t sec_mode0(int64_t n_pix, int64_t n_obs) {
     return ENC_HDR + up(2 * d, 16) + 7 * 2 * d;
 }
 static size_t table_bytes(int32_t n_chips) { return up(8 + 16 * ((size_t)n_chips + 1), ENC_ALIGN); }
+/* most bytes of a chip section in mode 2.  A run of k values at width w holds ceil(k w / 32) code
+ * words and e(w) exceptions: 4 ceil(k w / 32) + 2 e < (k w + 16 e) / 8 + 4 <= 2 k + 4, because the
+ * canonical w minimises k w + 16 e(w) and w = 16 costs 16 k.  So the codes and exceptions of a chip
+ * stay below mode 1's band columns + 4 bytes per run; added to mode 1's size: the run table
+ * (7 x 16 bytes per pixel), the pad word, and the alignment of the codes and exceptions parts. */
+static size_t sec_mode2_bound(int64_t n_pix, int64_t n_obs) {
+    return sec_mode1(n_pix, n_obs, n_pix * n_obs) + (112 + 28) * (size_t)n_pix + 4 + 32;
+}
 
-int64_t ccdgpu_encoded_bound(int32_t n_chips, const int32_t *n_pix, const int32_t *n_obs) {
-    if (n_chips <= 0 || !n_pix || !n_obs) return -1;
+int64_t ccdgpu_encoded_bound_flags(int32_t n_chips, const int32_t *n_pix, const int32_t *n_obs, uint32_t flags) {
+    if (n_chips <= 0 || !n_pix || !n_obs || (flags & ~CCDGPU_ENC_PACK)) return -1;
     size_t t = table_bytes(n_chips);
     for (int32_t c = 0; c < n_chips; ++c) {
-        const size_t a = sec_mode0(n_pix[c], n_obs[c]), b = sec_mode1(n_pix[c], n_obs[c], (int64_t)n_pix[c] * n_obs[c]);
+        const size_t a = sec_mode0(n_pix[c], n_obs[c]);
+        const size_t b = (flags & CCDGPU_ENC_PACK) ? sec_mode2_bound(n_pix[c], n_obs[c])
+                                                   : sec_mode1(n_pix[c], n_obs[c], (int64_t)n_pix[c] * n_obs[c]);
         t += up(a > b ? a : b, ENC_ALIGN);
     }
     return (int64_t)t;
+}
+int64_t ccdgpu_encoded_bound(int32_t n_chips, const int32_t *n_pix, const int32_t *n_obs) {
+    return ccdgpu_encoded_bound_flags(n_chips, n_pix, n_obs, 0);
 }
 
 /* ---- band compaction: dst[k++] = src[i] for the observations kept (keep[i] = 1); *bad is set
@@ -174,6 +190,26 @@ __attribute__((target("avx512f,avx512bw,avx512vbmi2"))) static size_t compact_vb
     *bad |= nb != 0;
     return k;
 }
+/* the same into a plain buffer (the packed encoder's staging row; dst holds n + 32 values: every
+ * step stores a whole register at the run's end) */
+__attribute__((target("avx512f,avx512bw,avx512vbmi2"))) static size_t compact_vbmi2_buf(const int16_t *src,
+                                                                                       const uint32_t *m,
+                                                                                       const uint32_t *sm, int n,
+                                                                                       int16_t *dst, int *bad) {
+    size_t k = 0;
+    int i = 0, w = 0;
+    const __m512i fillv = _mm512_set1_epi16(-9999);
+    __mmask32 nb = 0;
+    for (; i < n; i += 32, ++w) {
+        const __mmask32 lm = n - i >= 32 ? (__mmask32)0xFFFFFFFFu : (__mmask32)((1u << (n - i)) - 1u);
+        const __m512i v = _mm512_maskz_loadu_epi16(lm, (const void *)(src + i));
+        _mm512_storeu_si512((void *)(dst + k), _mm512_maskz_compress_epi16((__mmask32)(m[w] & lm), v));
+        k += (size_t)__builtin_popcount(m[w] & lm);
+        nb |= _mm512_mask_cmpneq_epi16_mask((__mmask32)(sm[w] & lm), v, fillv);
+    }
+    *bad |= nb != 0;
+    return k;
+}
 /* 4-bit palette codes (two per byte, even observation in the low nibble) and the keep bit masks
  * of one pixel's QA row, 32 observations at a time: a code is the index of the palette entry its
  * word equals (at most 16 compares); the codes' 16-bit lanes, read as 32-bit pairs, fold into
@@ -276,7 +312,9 @@ static int enc_block(void) {
 /* per-thread pass-1 state: the QA words seen (a 65536-bit set), a fill observation with a band
  * value other than -9999 */
 typedef struct {
-    uint8_t seen[65536];  /* scalar path: byte flags (independent stores, no read-modify-write chain) */
+    /* scalar path: byte flags (independent stores, no read-modify-write chain); 8-aligned in every
+     * element of the per-thread array, for the merge that reads them as 64-bit words */
+    uint8_t seen[65536] __attribute__((aligned(8)));
     uint16_t pal[17];     /* vector path: the distinct words met so far (17 = more than a palette holds) */
     int npal;
     int bad_fill;
@@ -312,10 +350,344 @@ static size_t encode_raw(int32_t n_pix, int32_t n_obs, const int16_t *spectra, c
  * words either way, so the bytes are the same. */
 #define ENC_SAMPLE 16
 
+/* ---- mode 2: bit-packed band runs (layout and the canonical width in include/ccdgpu.h) */
+typedef struct {
+    int16_t base;
+    uint16_t w;
+    uint32_t code_word, exc_off, n_exc;
+} pk_run_t;
+
+/* one run: the kept values v[0..k) of a (pixel, band) -> its descriptor (code_word / exc_off left
+ * to the caller), its code words at cw and its exceptions at ex; returns the code words written */
+static uint32_t pk_pack_run(const int16_t *v, int k, pk_run_t *r, uint32_t *cw, int16_t *ex) {
+    int mn = 0;
+    if (k > 0) {
+        mn = 32767;
+        for (int i = 0; i < k; ++i) mn = v[i] < mn ? v[i] : mn;
+    }
+    /* hist[j] = values with bitlen(r + 1) = j (1 .. 17): e(w) = the count of r >= 2^w - 1, that is
+     * of bitlen(r + 1) > w, is a suffix sum */
+    uint32_t hist[18] = {0};
+    for (int i = 0; i < k; ++i) hist[32 - __builtin_clz((uint32_t)(v[i] - mn) + 1u)]++;
+    int w = 0;
+    if (hist[1] != (uint32_t)k) {
+        uint32_t best = 0xFFFFFFFFu;
+        uint32_t suf[19];
+        suf[18] = 0;
+        for (int j = 17; j >= 1; --j) suf[j] = suf[j + 1] + hist[j];
+        for (int c = 1; c <= 16; ++c) {  /* ascending, strictly better only: ties go to the smallest w */
+            const uint32_t e = c < 16 ? suf[c + 1] : 0u;
+            const uint32_t cost = (uint32_t)c * (uint32_t)k + 16u * e;
+            if (cost < best) {
+                best = cost;
+                w = c;
+            }
+        }
+    }
+    r->base = (int16_t)mn;
+    r->w = (uint16_t)w;
+    uint32_t nw = 0, ne = 0;
+    if (w > 0) {
+        const uint32_t esc = w < 16 ? (1u << w) - 1u : 0xFFFFFFFFu;
+        uint64_t acc = 0;
+        int nb = 0;
+        for (int i = 0; i < k; ++i) {
+            uint32_t c = (uint32_t)(v[i] - mn);
+            if (c >= esc) {
+                c = esc;
+                ex[ne++] = v[i];
+            }
+            acc |= (uint64_t)c << nb;
+            nb += w;
+            if (nb >= 32) {
+                cw[nw++] = (uint32_t)acc;
+                acc >>= 32;
+                nb -= 32;
+            }
+        }
+        if (nb > 0) cw[nw++] = (uint32_t)acc;
+    }
+    r->n_exc = ne;
+    return nw;
+}
+
+#if defined(__x86_64__)
+__attribute__((target("avx512f,avx512bw"))) static inline int pk_min16(__m512i v) {
+    int16_t t[32] __attribute__((aligned(64)));
+    _mm512_store_si512((void *)t, v);
+    int m = t[0];
+    for (int i = 1; i < 32; ++i) m = t[i] < m ? t[i] : m;
+    return m;
+}
+__attribute__((target("avx512f,avx512bw"))) static inline unsigned pk_max16u(__m512i v) {
+    uint16_t t[32] __attribute__((aligned(64)));
+    _mm512_store_si512((void *)t, v);
+    unsigned m = t[0];
+    for (int i = 1; i < 32; ++i) m = t[i] > m ? t[i] : m;
+    return m;
+}
+/* pk_pack_run with AVX-512 (VBMI2 compress for the exceptions) and BMI2 pext for the bit packing:
+ * the same descriptor, words and exceptions (tests/test_encode_pack.py compares the bytes).  rb:
+ * k + 64 values of scratch; cw and ex may be written up to 16 words / 32 values past the run (the
+ * next run's place in the staging, or its slack).  The width search walks down from the narrowest
+ * width without escapes, W = bitlen(max r + 1) (cost W k), and stops at the first w whose escapes
+ * alone cost as much as the best so far: e(w) only grows below it, so nothing there can win or
+ * tie; going down, `<=` hands a tie to the smaller w, as the canonical choice wants. */
+__attribute__((target("avx512f,avx512bw,avx512vl,avx512vbmi2,bmi2"))) static uint32_t pk_pack_run_vec(
+    const int16_t *v, int k, pk_run_t *r, uint32_t *cw, int16_t *ex, uint16_t *rb) {
+    r->base = 0;
+    r->w = 0;
+    r->n_exc = 0;
+    if (k <= 0) return 0;
+    __m512i mnv = _mm512_set1_epi16(32767);
+    for (int i = 0; i < k; i += 32) {
+        const __mmask32 lm = k - i >= 32 ? (__mmask32)0xFFFFFFFFu : (__mmask32)((1u << (k - i)) - 1u);
+        mnv = _mm512_min_epi16(mnv, _mm512_mask_loadu_epi16(mnv, lm, (const void *)(v + i)));
+    }
+    const int mn = pk_min16(mnv);
+    r->base = (int16_t)mn;
+    const __m512i bv = _mm512_set1_epi16((short)mn);
+    __m512i mxv = _mm512_setzero_si512();
+    for (int i = 0; i < k; i += 32) {  /* residuals (mod 2^16 = the unsigned difference); 0 past the run */
+        const __mmask32 lm = k - i >= 32 ? (__mmask32)0xFFFFFFFFu : (__mmask32)((1u << (k - i)) - 1u);
+        const __m512i rr = _mm512_maskz_sub_epi16(lm, _mm512_maskz_loadu_epi16(lm, (const void *)(v + i)), bv);
+        _mm512_storeu_si512((void *)(rb + i), rr);
+        mxv = _mm512_max_epu16(mxv, rr);
+    }
+    _mm512_storeu_si512((void *)(rb + (k + 31) / 32 * 32), _mm512_setzero_si512());
+    const unsigned mx = pk_max16u(mxv);
+    if (mx == 0) return 0;
+    int W = 32 - __builtin_clz(mx + 1u);
+    if (W > 16) W = 16;
+    int w = W;
+    uint32_t best = (uint32_t)W * (uint32_t)k;
+    for (int c = W - 1; c >= 1; --c) {
+        const __m512i thr = _mm512_set1_epi16((short)((1u << c) - 1u));
+        uint32_t e = 0;
+        for (int i = 0; i < k; i += 32)
+            e += (uint32_t)__builtin_popcount(_mm512_cmpge_epu16_mask(_mm512_loadu_si512((const void *)(rb + i)), thr));
+        const uint32_t cost = (uint32_t)c * (uint32_t)k + 16u * e;
+        if (cost <= best) {
+            best = cost;
+            w = c;
+        }
+        if (16u * e >= best) break;
+    }
+    r->w = (uint16_t)w;
+    uint32_t ne = 0;
+    if (w < 16) {  /* codes in place of the residuals; the escapes' raw values to the exception list */
+        const __m512i escv = _mm512_set1_epi16((short)((1u << w) - 1u));
+        for (int i = 0; i < k; i += 32) {
+            const __m512i rr = _mm512_loadu_si512((const void *)(rb + i));
+            const __mmask32 m = _mm512_cmpge_epu16_mask(rr, escv);
+            _mm512_storeu_si512((void *)(rb + i), _mm512_min_epu16(rr, escv));
+            if (m) {
+                const __mmask32 lm = k - i >= 32 ? (__mmask32)0xFFFFFFFFu : (__mmask32)((1u << (k - i)) - 1u);
+                _mm512_storeu_si512((void *)(ex + ne),
+                                    _mm512_maskz_compress_epi16(m, _mm512_maskz_loadu_epi16(lm, (const void *)(v + i))));
+                ne += (uint32_t)__builtin_popcount(m);
+            }
+        }
+    }
+    r->n_exc = ne;
+    /* four codes at a time: pext gathers their low w bits into 4 w contiguous bits.  32 codes are
+     * exactly w words, so every chunk of 32 starts on a word with an empty accumulator: the chunks'
+     * shift / or chains do not depend on each other and overlap in the core.  The last chunk's
+     * codes past the run are 0 (rb is zero to the chunk's end); its words past the run's last one
+     * are zeros in the staging's next place or slack. */
+    const uint64_t pm = (uint64_t)((1u << w) - 1u) * 0x0001000100010001ull;
+    for (int ch = 0; ch < (k + 31) / 32; ++ch) {
+        const uint16_t *src = rb + 32 * ch;
+        uint32_t *o = cw + (size_t)ch * (size_t)w;
+        uint64_t acc = 0;
+        int nb = 0;
+#pragma GCC unroll 8
+        for (int g = 0; g < 8; ++g) {
+            uint64_t x;
+            memcpy(&x, src + 4 * g, 8);
+            x = _pext_u64(x, pm);
+            const uint64_t hi = nb ? x >> (64 - nb) : 0;
+            acc |= x << nb;
+            nb += 4 * w;
+            if (nb >= 64) {
+                memcpy(o, &acc, 8);
+                o += 2;
+                acc = hi;
+                nb -= 64;
+            }
+            if (nb >= 32) {
+                *o++ = (uint32_t)acc;
+                acc >>= 32;
+                nb -= 32;
+            }
+        }
+    }
+    return ((uint32_t)k * (uint32_t)w + 31u) / 32u;
+}
+#endif
+
+/* the scalar path's QA row: 4-bit codes, keep and strict flags per observation */
+static void pk_qa_scalar(const uint16_t *q, int n, const uint8_t *lut, uint16_t drop, uint16_t strict, uint8_t *r,
+                         uint8_t *keep, uint8_t *strictm) {
+    for (int i = 0; i < n; ++i) {
+        const uint16_t v = q[i];
+        if (i & 1) r[i >> 1] |= (uint8_t)(lut[v] << 4);
+        else r[i >> 1] = lut[v];
+        keep[i] = (uint8_t)!(v & drop);
+        strictm[i] = (uint8_t)((v & strict) != 0);
+    }
+}
+
+/* a block's staged code words into the section: the streaming writer where the vector path runs
+ * (full lines leave with non-temporal stores, the lines shared with the neighbouring blocks with
+ * masked stores of the block's own words), memcpy otherwise */
+#if defined(__x86_64__)
+__attribute__((target("avx512f,avx512bw"))) static void pk_stream_out(uint32_t *dst, const uint32_t *src, size_t words) {
+    ntw_t w;
+    const int16_t *s = (const int16_t *)src;
+    size_t n = 2 * words;
+    ntw_begin(&w, (int16_t *)dst);
+    for (; n >= 32; n -= 32, s += 32) ntw_put(&w, _mm512_loadu_si512((const void *)s), 32);
+    if (n) ntw_put(&w, _mm512_maskz_loadu_epi16((__mmask32)((1u << n) - 1u), (const void *)s), (int)n);
+    ntw_end(&w);
+}
+#endif
+
+/* pass 2 of a packed chip: QA codes, the run table, code words and exceptions behind the header,
+ * kept offsets and (already padded) code rows of `sec`.  Blocks of pixels are packed into
+ * thread-local staging (each raw row is read once) and committed in block order -- the ordered
+ * region hands out the block's first code word and exception -- so the prefix sums, and with them
+ * the bytes, do not depend on the thread count.  Returns the section's bytes; 0 when memory ran
+ * out; *miss / *bad as pass 2 of mode 1 reports them (the caller encodes again / sends raw);
+ * *bad also when the totals leave 32 bits. */
+static size_t pk_pass2(int32_t n_pix, int32_t n_obs, const int16_t *spectra, const uint16_t *qa, uint8_t *sec,
+                       uint8_t *q4, size_t rowb, const uint16_t *pal, int npal, const uint8_t *lut, uint16_t drop,
+                       uint16_t strict, int nt, int *miss_out, int *bad_out) {
+    const size_t plane = (size_t)n_pix * (size_t)n_obs;
+    pk_run_t *runs = (pk_run_t *)(q4 + up((size_t)n_pix * rowb, 16));
+    uint32_t *codes = (uint32_t *)(runs + 7 * (size_t)n_pix);
+    const int vec = have_vbmi2();
+    const int pb = enc_block();
+    const int mw = n_obs / 32 + 2;
+    const size_t rw = (size_t)n_obs / 2 + 1;  /* most code words of a run (w = 16) */
+    uint64_t g_cw = 0, g_ex = 0;              /* committed so far (ordered region only) */
+    int16_t *gex = NULL;                      /* the chip's exceptions until their place is known */
+    size_t gex_cap = 0;
+    int oom = 0, bad2 = 0, miss = 0;
+#pragma omp parallel num_threads(nt) reduction(| : bad2, miss)
+    {
+        int16_t *vals = (int16_t *)malloc(2 * ((size_t)n_obs + 64));
+        uint8_t *keep = (uint8_t *)malloc(2 * (size_t)n_obs + 64), *strictm = keep ? keep + n_obs + 32 : NULL;
+        uint32_t *km = (uint32_t *)malloc((size_t)mw * 8), *sm = km ? km + mw : NULL;
+        uint32_t *cw = (uint32_t *)malloc(4 * ((size_t)pb * 7 * rw + 32));             /* (+ the vector packer's slack) */
+        int16_t *ex = (int16_t *)malloc(2 * ((size_t)pb * 7 * (size_t)n_obs + 64));
+        uint16_t *rb = (uint16_t *)malloc(2 * ((size_t)n_obs + 128));
+        pk_run_t *rs = (pk_run_t *)malloc(sizeof(pk_run_t) * 7 * (size_t)pb);
+        const int ok = vals && keep && km && cw && ex && rs && rb;
+#pragma omp for schedule(static, 1) ordered
+        for (int32_t p0 = 0; p0 < n_pix; p0 += pb) {
+            const int32_t pe = p0 + pb < n_pix ? p0 + pb : n_pix;
+            uint32_t bw = 0, be = 0;  /* the block's code words and exceptions */
+            for (int32_t p = p0; ok && p < pe; ++p) {
+                const uint16_t *q = qa + (size_t)p * n_obs;
+#if defined(__x86_64__)
+                if (vec) miss |= qa_codes_avx512(q, n_obs, pal, npal, drop, strict, q4 + (size_t)p * rowb, km, sm);
+                else
+#endif
+                    pk_qa_scalar(q, n_obs, lut, drop, strict, q4 + (size_t)p * rowb, keep, strictm);
+                for (int b = 0; b < 7; ++b) {
+                    const int16_t *src = spectra + (size_t)b * plane + (size_t)p * n_obs;
+                    pk_run_t *r = rs + 7 * (size_t)(p - p0) + b;
+                    uint32_t nw;
+#if defined(__x86_64__)
+                    if (vec) {
+                        const size_t k = compact_vbmi2_buf(src, km, sm, n_obs, vals, &bad2);
+                        nw = pk_pack_run_vec(vals, (int)k, r, cw + bw, ex + be, rb);
+                    } else
+#endif
+                    {
+                        const size_t k = compact_scalar(src, keep, strictm, n_obs, vals, &bad2);
+                        nw = pk_pack_run(vals, (int)k, r, cw + bw, ex + be);
+                    }
+                    r->code_word = bw;
+                    r->exc_off = be;
+                    bw += nw;
+                    be += r->n_exc;
+                }
+            }
+            uint64_t my_cw = 0, my_ex = 0;
+#pragma omp ordered
+            {
+                my_cw = g_cw;
+                my_ex = g_ex;
+                g_cw += bw;
+                g_ex += be;
+                if (!ok) oom = 1;
+                if (be && !oom) {
+                    if (g_ex > gex_cap) {
+                        const size_t cap = (size_t)g_ex * 2 + 4096;
+                        int16_t *n = (int16_t *)realloc(gex, 2 * cap);
+                        if (n) {
+                            gex = n;
+                            gex_cap = cap;
+                        } else {
+                            oom = 1;
+                        }
+                    }
+                    if (!oom) memcpy(gex + my_ex, ex, 2 * (size_t)be);
+                }
+            }
+            if (!ok || my_cw + bw > 0xFFFFFFF0ull || my_ex + be > 0xFFFFFFF0ull) {
+                bad2 |= ok;  /* totals past 32 bits: the chip goes raw */
+                continue;
+            }
+            for (size_t i = 0; i < 7 * (size_t)(pe - p0); ++i) {
+                rs[i].code_word += (uint32_t)my_cw;
+                rs[i].exc_off += (uint32_t)my_ex;
+            }
+            memcpy(runs + 7 * (size_t)p0, rs, sizeof(pk_run_t) * 7 * (size_t)(pe - p0));
+#if defined(__x86_64__)
+            if (vec && bw) pk_stream_out(codes + my_cw, cw, bw);
+            else
+#endif
+                memcpy(codes + my_cw, cw, 4 * (size_t)bw);
+        }
+#if defined(__x86_64__)
+        if (vec) _mm_sfence();
+#endif
+        free(vals);
+        free(keep);
+        free(km);
+        free(cw);
+        free(ex);
+        free(rb);
+        free(rs);
+    }
+    *miss_out = miss;
+    *bad_out = bad2;
+    if (oom) {
+        free(gex);
+        return 0;
+    }
+    if (miss || bad2) {
+        free(gex);
+        return 1;  /* (any nonzero value: the caller looks at the flags first) */
+    }
+    /* the pad word and the padding of the codes part, then the exceptions */
+    const size_t cbytes = up(4 * ((size_t)g_cw + 1), 16);
+    memset(codes + g_cw, 0, cbytes - 4 * (size_t)g_cw);
+    int16_t *exc = (int16_t *)((uint8_t *)codes + cbytes);
+    if (g_ex) memcpy(exc, gex, 2 * (size_t)g_ex);
+    free(gex);
+    *(int64_t *)(sec + 88) = (int64_t)g_cw;
+    *(int64_t *)(sec + 96) = (int64_t)g_ex;
+    return (size_t)((uint8_t *)exc + 2 * (size_t)g_ex - sec);
+}
+
 /* one chip into sec (room for the larger of its two modes); returns the section's bytes */
 static size_t encode_chip(int32_t n_pix, int32_t n_obs, const int16_t *spectra, const uint16_t *qa, int64_t pix_base,
                           int64_t data_off, uint8_t *sec, int threads, uint32_t *kept_scratch, uint16_t drop,
-                          uint16_t strict) {
+                          uint16_t strict, uint32_t flags) {
     const size_t plane = (size_t)n_pix * (size_t)n_obs;
     int nt = threads > 0 ? threads : 1;
     if (nt > 64) nt = 64;
@@ -327,8 +699,13 @@ static size_t encode_chip(int32_t n_pix, int32_t n_obs, const int16_t *spectra, 
         return 0;
     }
     const int vec1 = have_vbmi2();
+    /* a packed chip of few observations can be larger than the raw chip (the run table is 112 bytes
+     * per pixel): such a chip is known to be encodable -- its full palette, its strict observations
+     * -- before pass 2 writes anything, so that a chip that goes raw after all never had bytes
+     * written behind the raw section the call returns */
+    const int pack_small = (flags & CCDGPU_ENC_PACK) && sec_mode2_bound(n_pix, n_obs) > sec_mode0(n_pix, n_obs);
     size_t ret = 0;
-    for (int full = vec1 ? 0 : 1; full < 2; ++full) {
+    for (int full = vec1 && !pack_small ? 0 : 1; full < 2; ++full) {
         const int sample = full ? 1 : ENC_SAMPLE;
         memset(st, 0, (size_t)nt * sizeof(pass1_t));
         /* pass 1: kept counts, distinct QA words (of the sampled pixels) */
@@ -413,6 +790,28 @@ static size_t encode_chip(int32_t n_pix, int32_t n_obs, const int16_t *spectra, 
         const size_t rowb = (size_t)(n_obs + 1) / 2;
         int16_t *bands = (int16_t *)(q4 + up((size_t)n_pix * rowb, 16));
         memset(q4 + (size_t)n_pix * rowb, 0, up((size_t)n_pix * rowb, 16) - (size_t)n_pix * rowb);
+        if (flags & CCDGPU_ENC_PACK) {  /* mode 2: the band runs bit-packed instead of the band columns */
+            int pmiss = 0, pbad = 0;
+            if (pack_small && strict) {
+#pragma omp parallel for schedule(static) num_threads(nt) reduction(| : pbad)
+                for (int32_t p = 0; p < n_pix; ++p)
+                    for (int32_t i = 0; i < n_obs; ++i)
+                        if (qa[(size_t)p * n_obs + i] & strict)
+                            for (int b = 0; b < 7; ++b)
+                                pbad |= spectra[(size_t)b * plane + (size_t)p * n_obs + i] != -9999;
+                if (pbad) {
+                    ret = encode_raw(n_pix, n_obs, spectra, qa, sec, nt);
+                    break;
+                }
+            }
+            h[0] = 2;
+            h64[2] = 0;
+            const size_t sz = pk_pass2(n_pix, n_obs, spectra, qa, sec, q4, rowb, pal, npal, lut, drop, strict, nt,
+                                       &pmiss, &pbad);
+            if (sz && pmiss && !full) continue;
+            ret = sz && pbad ? encode_raw(n_pix, n_obs, spectra, qa, sec, nt) : sz;
+            break;
+        }
         const int vec = have_vbmi2();
         int bad2 = 0, miss = 0;
         /* pass 2: 4-bit QA codes and the kept band values (and the fill observations' values checked).
@@ -501,9 +900,17 @@ static size_t encode_chip(int32_t n_pix, int32_t n_obs, const int16_t *spectra, 
 int64_t ccdgpu_encode_chips(int32_t n_chips, const int32_t *n_pix, const int32_t *n_obs, const int16_t *const *spectra,
                             const uint16_t *const *qa, uint8_t *out, int64_t out_cap, int32_t threads,
                             uint16_t drop_bits, uint16_t strict_bits) {
-    if (n_chips <= 0 || !n_pix || !n_obs || !spectra || !qa || !out) return -1;
+    return ccdgpu_encode_chips_flags(n_chips, n_pix, n_obs, spectra, qa, out, out_cap, threads, drop_bits, strict_bits,
+                                     0);
+}
+
+int64_t ccdgpu_encode_chips_flags(int32_t n_chips, const int32_t *n_pix, const int32_t *n_obs,
+                                  const int16_t *const *spectra, const uint16_t *const *qa, uint8_t *out,
+                                  int64_t out_cap, int32_t threads, uint16_t drop_bits, uint16_t strict_bits,
+                                  uint32_t flags) {
+    if (n_chips <= 0 || !n_pix || !n_obs || !spectra || !qa || !out || (flags & ~CCDGPU_ENC_PACK)) return -1;
     if ((strict_bits & ~drop_bits) != 0) return -1;  /* a strict observation is a dropped one */
-    const int64_t need = ccdgpu_encoded_bound(n_chips, n_pix, n_obs);
+    const int64_t need = ccdgpu_encoded_bound_flags(n_chips, n_pix, n_obs, flags);
     if (need < 0 || out_cap < need) return -2;
     int64_t *tab = (int64_t *)out;
     tab[0] = n_chips;
@@ -522,7 +929,7 @@ int64_t ccdgpu_encode_chips(int32_t n_chips, const int32_t *n_pix, const int32_t
         off[c] = (int64_t)pos;
         pix[c] = pbase;
         const size_t sz = encode_chip(n_pix[c], n_obs[c], spectra[c], qa[c], pbase, dbase, out + pos, threads, kept,
-                                      drop_bits, strict_bits);
+                                      drop_bits, strict_bits, flags);
         if (!sz) {
             free(kept);
             return -3;

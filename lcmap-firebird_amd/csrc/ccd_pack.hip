@@ -254,7 +254,156 @@ __global__ __launch_bounds__(256) void ccd_decode_enc(const unsigned char *__res
     }
 }
 
+// ---- batches with bit-packed band runs (mode 2 sections, include/ccdgpu.h; raw mode 0 chips of
+// the same batch are copied as above).  One wave per pixel, lane = observation, QA and kept rank
+// as in ccd_decode_enc.  Per band the wave reads the run's descriptor (wave-uniform), a kept lane
+// of rank r takes bits [r w, r w + w) from the two code words that hold them, and an escape code
+// (w = 1 .. 15, all ones) takes the raw value from the run's exception list at the lane's rank
+// among the escapes (a second ballot / mbcnt, carried per band across the chunks).  The host
+// check (ccdgpu_encoded_check) has tied every run's code_word / exc_off to the prefix sums of
+// ceil(k w / 32) and n_exc, so rank < k and erank < n_exc keep every load inside the section
+// whatever the code bits say; a lane outside them gets -9999.
+struct PackRun {
+    int16_t base;
+    uint16_t w;
+    uint32_t code_word, exc_off, n_exc;
+};
+static_assert(sizeof(PackRun) == 16, "run descriptor layout");
+
+__global__ __launch_bounds__(256) void ccd_decode_pack(const unsigned char *__restrict__ enc, int64_t total_pix,
+                                                        int16_t *__restrict__ spectra, uint16_t *__restrict__ qa) {
+    const int64_t pix = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (pix >= total_pix) return;
+    const int l = threadIdx.x & 63;
+    const int64_t *tab = reinterpret_cast<const int64_t *>(enc);
+    const int64_t nc = tab[0];
+    const int64_t *off = tab + 1, *pixo = tab + 2 + nc;
+    int64_t lo = 0, hi = nc - 1;  // the pixel's chip (wave-uniform binary search)
+    while (lo < hi) {
+        const int64_t mid = (lo + hi + 1) >> 1;
+        if (pixo[mid] <= pix) lo = mid;
+        else hi = mid - 1;
+    }
+    const unsigned char *sec = enc + off[lo];
+    const int32_t *h = reinterpret_cast<const int32_t *>(sec);
+    const int mode = h[0], n_pix = h[1], n_obs = h[2];
+    const int64_t *h64 = reinterpret_cast<const int64_t *>(sec + 48);
+    const int64_t data_off = h64[1];
+    const int64_t p = pix - pixo[lo];
+    const int64_t plane = (int64_t)n_pix * n_obs;
+    int16_t *sp = spectra + 7 * data_off + p * n_obs;
+    uint16_t *qo = qa + data_off + p * n_obs;
+    if (mode != 2) {  // raw (the host check admits only modes 0 and 2 here)
+        const uint16_t *rq = reinterpret_cast<const uint16_t *>(sec + ENC_HDR) + p * n_obs;
+        const int16_t *rs = reinterpret_cast<const int16_t *>(sec + ENC_HDR + up16(2 * plane)) + p * n_obs;
+        for (int i = l; i < n_obs; i += 64) {
+            qo[i] = rq[i];
+#pragma unroll
+            for (int b = 0; b < 7; ++b) sp[(int64_t)b * plane + i] = rs[(int64_t)b * plane + i];
+        }
+        return;
+    }
+    const uint16_t palr = l < 16 ? reinterpret_cast<const uint16_t *>(sec + 16)[l] : (uint16_t)0;
+    const unsigned drop = *reinterpret_cast<const uint32_t *>(sec + 80);
+    const int64_t code_words = h64[5];  // byte 88
+    const uint32_t *koff = reinterpret_cast<const uint32_t *>(sec + ENC_HDR);
+    const unsigned char *q4 = sec + ENC_HDR + up16(4 * ((int64_t)n_pix + 1));
+    const int64_t rowb = (n_obs + 1) / 2;
+    const PackRun *runs = reinterpret_cast<const PackRun *>(q4 + up16((int64_t)n_pix * rowb));
+    const uint32_t *codes = reinterpret_cast<const uint32_t *>(runs + 7 * (int64_t)n_pix);
+    const int16_t *exc = reinterpret_cast<const int16_t *>(reinterpret_cast<const unsigned char *>(codes) +
+                                                           up16(4 * (code_words + 1)));
+    const int kcount = (int)(koff[p + 1] - koff[p]);
+    const unsigned char *qr = q4 + p * rowb;
+    // the pixel's seven descriptors (112 contiguous bytes, the same for every lane)
+    PackRun run[7];
+#pragma unroll
+    for (int b = 0; b < 7; ++b) {
+        const uint4 d = reinterpret_cast<const uint4 *>(runs + 7 * p)[b];
+        run[b].base = (int16_t)(d.x & 0xFFFFu);
+        run[b].w = (uint16_t)(d.x >> 16);
+        run[b].code_word = d.y;
+        run[b].exc_off = d.z;
+        run[b].n_exc = d.w;
+    }
+    int carry = 0;
+    int ecarry[7] = {0, 0, 0, 0, 0, 0, 0};
+    // two 64-observation chunks per round: code bytes, ranks, then every band's code words go out
+    // before the exception loads that depend on them and before the first store
+    constexpr int U = 2;
+    for (int i0 = 0; i0 < n_obs; i0 += U * 64) {
+        unsigned cb[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int i = i0 + u * 64 + l;
+            cb[u] = i < n_obs ? (unsigned)qr[i >> 1] : 0u;
+        }
+        uint16_t q[U];
+        bool keep[U];
+        int rank[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int i = i0 + u * 64 + l;
+            const bool in = i < n_obs;
+            const int code = (int)((cb[u] >> ((i & 1) * 4)) & 15u);
+            q[u] = (uint16_t)__shfl((int)palr, code, 64);
+            const bool kp = in && !(q[u] & drop);
+            const unsigned long long km = __ballot(kp);
+            rank[u] = carry + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(km >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)km, 0));
+            carry += __popcll(km);
+            keep[u] = kp && rank[u] < kcount;  // a code row claiming more than the run holds: -9999
+        }
+        unsigned long long cw[U][7];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+#pragma unroll
+            for (int b = 0; b < 7; ++b) {
+                cw[u][b] = 0ull;
+                const unsigned w = run[b].w;
+                if (keep[u] && w) {  // words wi and wi + 1 <= the run's last word + 1 (the pad word at the end)
+                    const uint32_t *c = codes + run[b].code_word + (((unsigned)rank[u] * w) >> 5);
+                    cw[u][b] = (unsigned long long)c[0] | ((unsigned long long)c[1] << 32);
+                }
+            }
+        }
+        int16_t v[U][7];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+#pragma unroll
+            for (int b = 0; b < 7; ++b) {
+                const unsigned w = run[b].w;
+                const unsigned esc = (1u << w) - 1u;  // (w = 16: 0xFFFF, never an escape)
+                const unsigned code = (unsigned)(cw[u][b] >> (((unsigned)rank[u] * w) & 31u)) & esc;
+                const bool is_esc = keep[u] && w >= 1 && w <= 15 && code == esc;
+                const unsigned long long em = __ballot(is_esc);  // (wave-uniform control flow up to here)
+                const int erank = ecarry[b] + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(em >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)em, 0));
+                ecarry[b] += __popcll(em);
+                int16_t val = keep[u] ? (int16_t)(run[b].base + (int)code) : (int16_t)-9999;
+                if (is_esc) val = (unsigned)erank < run[b].n_exc ? exc[run[b].exc_off + (unsigned)erank] : (int16_t)-9999;
+                v[u][b] = val;
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int i = i0 + u * 64 + l;
+            if (i < n_obs) {
+                qo[i] = q[u];
+#pragma unroll
+                for (int b = 0; b < 7; ++b) sp[(int64_t)b * plane + i] = v[u][b];
+            }
+        }
+    }
+}
+
 }  // namespace
+
+extern "C" int ccdk_decode_pack(const unsigned char *enc, int64_t total_pix, int16_t *spectra, uint16_t *qa,
+                                void *stream) {
+    if (total_pix <= 0) return 0;
+    hipLaunchKernelGGL(ccd_decode_pack, dim3((unsigned)((total_pix + 3) / 4)), dim3(256), 0, (hipStream_t)stream, enc,
+                       total_pix, spectra, qa);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
 
 extern "C" int ccdk_decode_enc(const unsigned char *enc, int64_t total_pix, int16_t *spectra, uint16_t *qa,
                                void *stream) {

@@ -751,8 +751,11 @@ int ccdgpu_stage_slot_chips(ccdgpu_ctx *c, int32_t slot, const ccdgpu_params *pa
     return 0;
 }
 
-int ccdgpu_encoded_check(int32_t n_chips, const int32_t *n_pix, const int32_t *n_obs, const uint8_t *enc,
-                         int64_t enc_bytes) {
+// ccdgpu_encoded_check; *packed: the batch holds a mode 2 section (it goes to ccd_decode_pack)
+static int encoded_check(int32_t n_chips, const int32_t *n_pix, const int32_t *n_obs, const uint8_t *enc,
+                         int64_t enc_bytes, bool *packed) {
+    *packed = false;
+    bool mode1 = false;
     if (!enc || !n_pix || !n_obs || n_chips <= 0) return fail(CCDGPU_EINVAL, "NULL or empty encoded batch");
     // the encoded batch must describe exactly these chips (the decoder trusts its headers)
     const int64_t *tab = reinterpret_cast<const int64_t *>(enc);
@@ -768,8 +771,8 @@ int ccdgpu_encoded_check(int32_t n_chips, const int32_t *n_pix, const int32_t *n
             return fail(CCDGPU_EINVAL, "encoded batch: bad chip table entry " + std::to_string(k));
         const int32_t *h = reinterpret_cast<const int32_t *>(enc + off[k]);
         const int64_t *h64 = reinterpret_cast<const int64_t *>(enc + off[k] + 48);
-        if ((h[0] != 0 && h[0] != 1) || h[1] != n_pix[k] || h[2] != n_obs[k] || h64[1] != db ||
-            (h[0] == 1 && (h[3] < 1 || h[3] > 16)))
+        if ((h[0] != 0 && h[0] != 1 && h[0] != 2) || h[1] != n_pix[k] || h[2] != n_obs[k] || h64[1] != db ||
+            (h[0] != 0 && (h[3] < 1 || h[3] > 16)))
             return fail(CCDGPU_EINVAL, "encoded batch: chip " + std::to_string(k) + " header does not match its shape");
         // the section holds everything its mode's layout addresses (the decoder trusts it)
         const int64_t np_ = n_pix[k], no_ = n_obs[k], plane = np_ * no_, sec = off[k + 1] - off[k];
@@ -777,7 +780,48 @@ int ccdgpu_encoded_check(int32_t n_chips, const int32_t *n_pix, const int32_t *n
         if (h[0] == 0) {
             if (sec < 128 + up_(2 * plane, 16) + 14 * plane)
                 return fail(CCDGPU_EINVAL, "encoded batch: chip " + std::to_string(k) + " raw section is truncated");
+        } else if (h[0] == 2) {
+            // bit-packed runs: the kept table as in mode 1, then every run's descriptor against the
+            // prefix sums of its code words (ceil(k w / 32)) and exceptions, the totals against the
+            // header, and the section long enough for all five parts and the pad word -- after
+            // this no code bit can send the decoder outside the section
+            *packed = true;
+            const std::string chip = "encoded batch: chip " + std::to_string(k);
+            const int64_t kept = h64[0], code_words = h64[5], exc_total = h64[6];
+            const int64_t runs_at = 128 + up_(4 * (np_ + 1), 16) + up_(np_ * ((no_ + 1) / 2), 16);
+            const int64_t codes_at = runs_at + 112 * np_;
+            if (kept < 0 || kept > plane || h64[2] != 0 || code_words < 0 || exc_total < 0 ||
+                code_words > 4 * plane + 8 * np_ || exc_total > 7 * plane || sec < codes_at)
+                return fail(CCDGPU_EINVAL, chip + " packed header does not fit its section");
+            const uint32_t *koff = reinterpret_cast<const uint32_t *>(enc + off[k] + 128);
+            if (koff[0] != 0 || (int64_t)koff[np_] != kept)
+                return fail(CCDGPU_EINVAL, chip + " kept-offset table does not end at kept");
+            for (int64_t q = 0; q < np_; ++q)
+                if (koff[q + 1] < koff[q] || (int64_t)(koff[q + 1] - koff[q]) > no_)
+                    return fail(CCDGPU_EINVAL, chip + " kept-offset table is not a run per pixel");
+            const uint8_t *runs = enc + off[k] + runs_at;
+            int64_t cw = 0, ex = 0;
+            for (int64_t r = 0; r < 7 * np_; ++r) {
+                const uint8_t *d = runs + 16 * r;
+                uint16_t w;
+                uint32_t f[3];
+                std::memcpy(&w, d + 2, 2);
+                std::memcpy(f, d + 4, 12);
+                const int64_t kk = (int64_t)(koff[r / 7 + 1] - koff[r / 7]);
+                if (w > 16) return fail(CCDGPU_EINVAL, chip + " run " + std::to_string(r) + " has a width above 16");
+                if ((int64_t)f[0] != cw || (int64_t)f[1] != ex)
+                    return fail(CCDGPU_EINVAL, chip + " run " + std::to_string(r) + " does not start at the prefix sums");
+                if ((int64_t)f[2] > kk)
+                    return fail(CCDGPU_EINVAL, chip + " run " + std::to_string(r) + " has more exceptions than values");
+                cw += (kk * w + 31) / 32;
+                ex += f[2];
+            }
+            if (cw != code_words || ex != exc_total)
+                return fail(CCDGPU_EINVAL, chip + " run totals do not match code_words / exc_total");
+            if (sec < codes_at + up_(4 * (code_words + 1), 16) + 2 * exc_total)
+                return fail(CCDGPU_EINVAL, chip + " packed section is truncated");
         } else {
+            mode1 = true;
             const int64_t kept = h64[0], bstride = h64[2];
             const int64_t bands_at = 128 + up_(4 * (np_ + 1), 16) + up_(np_ * ((no_ + 1) / 2), 16);
             if (kept < 0 || kept > plane || bstride < kept || bstride % 8 != 0 || sec < bands_at + 14 * bstride)
@@ -793,7 +837,14 @@ int ccdgpu_encoded_check(int32_t n_chips, const int32_t *n_pix, const int32_t *n
         db += (int64_t)n_pix[k] * n_obs[k];
     }
     if (pixo[n_chips] != pb) return fail(CCDGPU_EINVAL, "encoded batch: pixel total does not match");
+    if (mode1 && *packed) return fail(CCDGPU_EINVAL, "encoded batch: mode 1 and mode 2 sections in one batch");
     return 0;
+}
+
+int ccdgpu_encoded_check(int32_t n_chips, const int32_t *n_pix, const int32_t *n_obs, const uint8_t *enc,
+                         int64_t enc_bytes) {
+    bool packed;
+    return encoded_check(n_chips, n_pix, n_obs, enc, enc_bytes, &packed);
 }
 
 int ccdgpu_stage_slot_encoded(ccdgpu_ctx *c, int32_t slot, const ccdgpu_params *params, int32_t n_chips,
@@ -808,14 +859,18 @@ int ccdgpu_stage_slot_encoded(ccdgpu_ctx *c, int32_t slot, const ccdgpu_params *
     Shape sh;
     int rc = make_shape(n_chips, n_pix, n_obs, sh);
     if (rc || (rc = check_params(params))) return rc;
-    if ((rc = ccdgpu_encoded_check(n_chips, n_pix, n_obs, enc, enc_bytes))) return rc;
+    bool packed = false;
+    if ((rc = encoded_check(n_chips, n_pix, n_obs, enc, enc_bytes, &packed))) return rc;
+    // a batch with bit-packed sections is always decoded into the slot's standard buffers (the
+    // detection kernel reads modes 0 and 1 in place, not mode 2)
+    const bool decode = c->decode_enc || packed;
     const int64_t *off = reinterpret_cast<const int64_t *>(enc) + 1;
     const int64_t pb = sh.total_pix();
     HIPCHK(hipSetDevice(c->device));
     const size_t tobs = (size_t)sh.total_obs(), tdata = (size_t)sh.total_data();
     if ((rc = c->slot_dates[slot].ensure(tobs)) || (rc = c->slot_enc[slot].ensure((size_t)off[n_chips])))
         return rc;
-    if (c->decode_enc && ((rc = c->slot_spectra[slot].ensure(7 * tdata)) || (rc = c->slot_qa[slot].ensure(tdata))))
+    if (decode && ((rc = c->slot_spectra[slot].ensure(7 * tdata)) || (rc = c->slot_qa[slot].ensure(tdata))))
         return rc;
     // upload on the copy stream; the detection kernel reads the encoded batch in place (no decode
     // pass: px_setup in ccd_kernels.hip), or -- CCDGPU_DECODE=1 -- it is decoded there into the
@@ -823,16 +878,19 @@ int ccdgpu_stage_slot_encoded(ccdgpu_ctx *c, int32_t slot, const ccdgpu_params *
     HIPCHK(hipMemcpyAsync(c->slot_dates[slot].p, dates, sizeof(int64_t) * tobs, hipMemcpyHostToDevice, c->up_stream));
     HIPCHK(hipMemcpyAsync(c->slot_enc[slot].p, enc, (size_t)off[n_chips], hipMemcpyHostToDevice, c->up_stream));
     HIPCHK(hipEventRecord(c->uploaded[slot], c->up_stream));
-    if (c->decode_enc) {
+    if (decode) {
         if (c->up_stream != c->copy_stream) HIPCHK(hipStreamWaitEvent(c->copy_stream, c->uploaded[slot], 0));
-        if (ccdk_decode_enc(c->slot_enc[slot].p, pb, c->slot_spectra[slot].p, c->slot_qa[slot].p, c->copy_stream))
+        if (packed) {
+            if (ccdk_decode_pack(c->slot_enc[slot].p, pb, c->slot_spectra[slot].p, c->slot_qa[slot].p, c->copy_stream))
+                return fail(CCDGPU_EHIP, "ccd_decode_pack launch failed");
+        } else if (ccdk_decode_enc(c->slot_enc[slot].p, pb, c->slot_spectra[slot].p, c->slot_qa[slot].p, c->copy_stream))
             return fail(CCDGPU_EHIP, "ccd_decode_enc launch failed");
         HIPCHK(hipEventRecord(c->uploaded[slot], c->copy_stream));
     }
     c->slot_shape[slot] = sh;
     c->slot_params[slot] = *params;
     c->slot_ready[slot] = true;
-    c->slot_encoded[slot] = !c->decode_enc;
+    c->slot_encoded[slot] = !decode;
     return 0;
 }
 

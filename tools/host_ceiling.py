@@ -7,7 +7,8 @@ encoded bytes streamed; plus the DMA's read of the encoded bytes when uploaded a
 so the per-socket memory ceiling of the tile's host side can be read off where the aggregate
 stops scaling with K.
 
-usage: host_ceiling.py [chips_per_thread] [seconds_per_point]"""
+usage: host_ceiling.py [--pack] [--lossless] [chips_per_thread] [seconds_per_point]
+--pack: the bit-packed mode 2 of the encoding (EncodedBatch(pack=True)); --lossless: drop only fill."""
 import os
 import sys
 import threading
@@ -21,8 +22,10 @@ from ccdgpu import synth  # noqa: E402
 
 
 def main():
-    per = int(sys.argv[1]) if len(sys.argv) > 1 else 6
-    secs = float(sys.argv[2]) if len(sys.argv) > 2 else 6.0
+    pack, lossless = '--pack' in sys.argv, '--lossless' in sys.argv
+    argv = [a for a in sys.argv[1:] if not a.startswith('--')]
+    per = int(argv[0]) if len(argv) > 0 else 6
+    secs = float(argv[1]) if len(argv) > 1 else 6.0
     K_MAX, T = 5, 3
     cfg = synth.config(3)
     from ccdc import runner
@@ -33,16 +36,17 @@ def main():
         b = g.batch(cfg, list(range(1000 + per * k, 1000 + per * (k + 1))), pinned=False)
         pools.append([tuple(np.array(a) for a in b.chip(j)) for j in range(b.n_chips)])
     g.close()
-    drop, strict = ccdgpu.unread_drop_bits(None)
+    drop, strict = (1, 1) if lossless else ccdgpu.unread_drop_bits(None)
     raw_per = [sum(s.nbytes + q.nbytes for _, s, q in p) for p in pools]
-    out = {'chips_per_thread': per, 'omp_threads_per_encoder': T, 'cpu_quota_threads': os.environ.get('OMP_NUM_THREADS')}
+    out = {'pack': pack, 'drop': 'lossless' if lossless else 'unread', 'chips_per_thread': per, 'omp_threads_per_encoder': T, 'cpu_quota_threads': os.environ.get('OMP_NUM_THREADS')}
     for K in range(1, K_MAX + 1):
         stop = threading.Event()
         done = [0] * K
         sent = [0] * K
 
         def work(k):
-            e = ccdgpu.EncodedBatch([q.shape[0] for _, _, q in pools[k]], [d.shape[0] for d, _, _ in pools[k]], pinned=True)
+            e = ccdgpu.EncodedBatch([q.shape[0] for _, _, q in pools[k]], [d.shape[0] for d, _, _ in pools[k]], pinned=True,
+                                    pack=pack)
             while not stop.is_set():
                 sent[k] += e.fill(pools[k], threads=T, drop_bits=drop, strict_bits=strict)
                 done[k] += 1
