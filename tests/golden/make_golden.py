@@ -17,11 +17,12 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
-sys.path[:0] = [os.path.join(ROOT, 'lcmap-firebird_amd'), os.path.join(ROOT, 'oracle')]
+sys.path[:0] = [os.path.join(ROOT, 'lcmap-firebird_amd'), os.path.join(ROOT, 'oracle'), os.path.join(ROOT, 'tests')]
 
 import numpy as np  # noqa: E402
 
 import ccd_ref  # noqa: E402
+import degenerate_util  # noqa: E402
 from ccdgpu import abi, synth  # noqa: E402
 
 
@@ -268,6 +269,11 @@ def main():
     cases['dup_shuffled_stable'] = (cases['dup_shuffled'][0], {'ARGSORT': 'stable'})
     cases['tie_cycles'] = (tie_cycles_case(), None)
     cases['tie_cycles_stable'] = (tie_cycles_case(), {'ARGSORT': 'stable'})
+    # zero-variogram, flat and exact-fit pixels (tests/degenerate_util.py: the defined recipes);
+    # all seven detection bands take the kernel's other peek-magnitude instantiation
+    cases['degenerate_16d'] = (degenerate_util.defined('16d'), None)
+    cases['degenerate_4d'] = (degenerate_util.defined('4d'), None)
+    cases['degenerate_16d_allbands'] = (degenerate_util.defined('16d'), {'DETECTION_BANDS': [0, 1, 2, 3, 4, 5, 6]})
     with multiprocessing.Pool(min(8, os.cpu_count() or 1)) as pool:
         for name, ((d, s, q), params) in cases.items():
             if only and name not in only:

@@ -47,12 +47,23 @@ def compare(got, ref, rtol=RTOL, atol=ATOL, max_report=10):
                     problems.append('px %d seg %d %s %s vs %s' % (px, k, f, g[f], r[f]))
             for f in FLOAT_FIELDS:
                 a, b = np.asarray(g[f], dtype=np.float64), np.asarray(r[f], dtype=np.float64)
-                diff = np.abs(a - b)
-                scale = np.maximum(np.abs(a), np.abs(b))
-                bad = diff > rtol * scale + atol
+                # a non-finite value matches only its own kind in the same place (NaN with NaN,
+                # an inf with the inf of its sign); such matched pairs are equal and take no part
+                # in max_rel, any other non-finite value is a problem (max_rel inf)
+                fin = np.isfinite(a) & np.isfinite(b)
+                same = (np.isnan(a) & np.isnan(b)) | (np.isinf(a) & np.isinf(b) & (a == b))
+                wrong = ~fin & ~same
                 with np.errstate(divide='ignore', invalid='ignore'):
+                    diff = np.where(fin, np.abs(a - b), 0.0)
+                    scale = np.where(fin, np.maximum(np.abs(a), np.abs(b)), 0.0)
                     rel = np.where(scale > 0, diff / scale, 0.0)
+                bad = diff > rtol * scale + atol
                 max_rel = max(max_rel, float(np.max(rel)) if rel.size else 0.0)
+                if np.any(wrong):
+                    max_rel = np.inf
+                    i = int(np.flatnonzero(wrong.reshape(-1))[0])
+                    problems.append('px %d seg %d %s non-finite: %r vs %r' % (px, k, f, float(a.reshape(-1)[i]),
+                                                                             float(b.reshape(-1)[i])))
                 if np.any(bad):
                     problems.append('px %d seg %d %s max rel %.3e' % (px, k, f, float(np.max(rel))))
     return problems, max_rel
