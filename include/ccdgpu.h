@@ -259,7 +259,9 @@ int ccdgpu_run_slot_end_rows(ccdgpu_ctx *ctx, double *kernel_seconds, int64_t *n
  * `strict_bits` (a subset of drop_bits) its 7 bands must all be -9999 or the chip is sent raw --
  * drop_bits = strict_bits = the fill bit is lossless; adding the cloud and shadow bits drops
  * only values the detection never reads (ccd_encode.c); QA words become 4-bit indices into the
- * chip's palette when it has at most 16 distinct words, else the chip is sent raw.  Layout:
+ * chip's palette when it has at most 16 distinct words, else the chip is sent raw.  Layout (this
+ * text is normative; lcmap-firebird_amd/csrc/ccd_enc_layout.h is its one definition in code, with
+ * the byte offsets below asserted at compile time):
  *   int64 n_chips; int64 chip_off[n_chips + 1] (bytes from `out`, 256-aligned);
  *   int64 chip_pix[n_chips + 1] (pixel prefix); chip sections:
  *   header (128 B): int32 mode (0 raw, 1 encoded), n_pix, n_obs, n_pal; uint16 pal[16];

@@ -16,7 +16,8 @@
  *     16-entry palette (a chip with more distinct words is sent raw, mode 0).
  * The device decoder (ccd_decode_enc in ccd_pack.hip) rebuilds the standard band-major
  * [7][n_pix][n_obs] spectra and [n_pix][n_obs] QA of every chip (tests/test_encode.py: round
- * trips against a numpy decoder).  Layout: include/ccdgpu.h.
+ * trips against a numpy decoder).  Layout: described in include/ccdgpu.h, defined (offsets, part
+ * locators, section sizes) in ccd_enc_layout.h.
  *   - with CCDGPU_ENC_PACK (ccdgpu_encode_chips_flags) the kept band values of each (pixel, band)
  *     travel as a base, a bit width and bit-packed residuals with an exception list (mode 2,
  *     decoded by ccd_decode_pack; tests/test_encode_pack.py) instead of as int16 columns.
@@ -29,45 +30,24 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "ccd_enc_layout.h"
 #include "ccdgpu.h"
 #ifdef _OPENMP
 #include <omp.h>
 #endif
 
-#define ENC_HDR 128
-#define ENC_ALIGN 256
-
-static size_t up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
-/* bytes of a chip section in mode 1 for kept observations, and in mode 0 */
-static size_t sec_mode1(int64_t n_pix, int64_t n_obs, int64_t kept) {
-    return ENC_HDR + up(4 * (size_t)(n_pix + 1), 16) + up((size_t)n_pix * (size_t)((n_obs + 1) / 2), 16) +
-           7 * 2 * up((size_t)kept, 8);
-}
-static size_t sec_mode0(int64_t n_pix, int64_t n_obs) {
-    const size_t d = (size_t)n_pix * (size_t)n_obs;
-    return ENC_HDR + up(2 * d, 16) + 7 * 2 * d;
-}
-static size_t table_bytes(int32_t n_chips) { return up(8 + 16 * ((size_t)n_chips + 1), ENC_ALIGN); }
-/* most bytes of a chip section in mode 2.  A run of k values at width w holds ceil(k w / 32) code
- * words and e(w) exceptions: 4 ceil(k w / 32) + 2 e < (k w + 16 e) / 8 + 4 <= 2 k + 4, because the
- * canonical w minimises k w + 16 e(w) and w = 16 costs 16 k.  So the codes and exceptions of a chip
- * stay below mode 1's band columns + 4 bytes per run; added to mode 1's size: the run table
- * (7 x 16 bytes per pixel), the pad word, and the alignment of the codes and exceptions parts. */
-static size_t sec_mode2_bound(int64_t n_pix, int64_t n_obs) {
-    return sec_mode1(n_pix, n_obs, n_pix * n_obs) + (112 + 28) * (size_t)n_pix + 4 + 32;
-}
-
 int64_t ccdgpu_encoded_bound_flags(int32_t n_chips, const int32_t *n_pix, const int32_t *n_obs, uint32_t flags) {
     if (n_chips <= 0 || !n_pix || !n_obs || (flags & ~CCDGPU_ENC_PACK)) return -1;
-    size_t t = table_bytes(n_chips);
+    int64_t t = ccd_enc_table_bytes(n_chips);
     for (int32_t c = 0; c < n_chips; ++c) {
-        const size_t a = sec_mode0(n_pix[c], n_obs[c]);
-        const size_t b = (flags & CCDGPU_ENC_PACK) ? sec_mode2_bound(n_pix[c], n_obs[c])
-                                                   : sec_mode1(n_pix[c], n_obs[c], (int64_t)n_pix[c] * n_obs[c]);
-        t += up(a > b ? a : b, ENC_ALIGN);
+        const int64_t plane = (int64_t)n_pix[c] * n_obs[c];
+        const int64_t a = ccd_enc_size_raw(plane);
+        const int64_t b = (flags & CCDGPU_ENC_PACK)
+                              ? ccd_enc_size_pack_bound(n_pix[c], n_obs[c])
+                              : ccd_enc_size_cols(n_pix[c], n_obs[c], ccd_enc_band_stride(plane));
+        t += ccd_enc_up_align(a > b ? a : b);
     }
-    return (int64_t)t;
+    return t;
 }
 int64_t ccdgpu_encoded_bound(int32_t n_chips, const int32_t *n_pix, const int32_t *n_obs) {
     return ccdgpu_encoded_bound_flags(n_chips, n_pix, n_obs, 0);
@@ -324,16 +304,15 @@ typedef struct {
 static size_t encode_raw(int32_t n_pix, int32_t n_obs, const int16_t *spectra, const uint16_t *qa, uint8_t *sec,
                          int nt) {
     const size_t plane = (size_t)n_pix * (size_t)n_obs;
-    int32_t *h = (int32_t *)sec;
-    h[0] = 0;
-    h[3] = 0;
-    int64_t *h64 = (int64_t *)(sec + 48);
-    h64[0] = 0;
-    h64[2] = 0;
-    memset(sec + 16, 0, 32);
-    uint16_t *oq = (uint16_t *)(sec + ENC_HDR);
-    int16_t *os = (int16_t *)(sec + ENC_HDR + up(2 * plane, 16));
-    memset((uint8_t *)(oq + plane), 0, up(2 * plane, 16) - 2 * plane);
+    ccd_enc_hdr *h = (ccd_enc_hdr *)sec;
+    h->mode = CCD_ENC_MODE_RAW;
+    h->n_pal = 0;
+    h->kept = 0;
+    h->band_stride = 0;
+    memset(h->pal, 0, sizeof h->pal);
+    uint16_t *oq = (uint16_t *)ccd_enc_raw_qa(sec);
+    int16_t *os = (int16_t *)ccd_enc_raw_spectra(sec, (int64_t)plane);
+    memset(oq + plane, 0, (size_t)ccd_enc_raw_qa_bytes((int64_t)plane) - 2 * plane);
 #pragma omp parallel for schedule(static) num_threads(nt)
     for (int32_t p = 0; p < n_pix; ++p) {
         memcpy(oq + (size_t)p * n_obs, qa + (size_t)p * n_obs, 2 * (size_t)n_obs);
@@ -341,7 +320,7 @@ static size_t encode_raw(int32_t n_pix, int32_t n_obs, const int16_t *spectra, c
             memcpy(os + (size_t)b * plane + (size_t)p * n_obs, spectra + (size_t)b * plane + (size_t)p * n_obs,
                    2 * (size_t)n_obs);
     }
-    return sec_mode0(n_pix, n_obs);
+    return (size_t)ccd_enc_size_raw((int64_t)plane);
 }
 
 /* pixels of a chip whose QA rows pass 1 scans for the palette (vector path): every
@@ -350,16 +329,12 @@ static size_t encode_raw(int32_t n_pix, int32_t n_obs, const int16_t *spectra, c
  * words either way, so the bytes are the same. */
 #define ENC_SAMPLE 16
 
-/* ---- mode 2: bit-packed band runs (layout and the canonical width in include/ccdgpu.h) */
-typedef struct {
-    int16_t base;
-    uint16_t w;
-    uint32_t code_word, exc_off, n_exc;
-} pk_run_t;
+/* ---- mode 2: bit-packed band runs (layout and the canonical width in include/ccdgpu.h; the run
+ * descriptor ccd_enc_run in ccd_enc_layout.h) */
 
 /* one run: the kept values v[0..k) of a (pixel, band) -> its descriptor (code_word / exc_off left
  * to the caller), its code words at cw and its exceptions at ex; returns the code words written */
-static uint32_t pk_pack_run(const int16_t *v, int k, pk_run_t *r, uint32_t *cw, int16_t *ex) {
+static uint32_t pk_pack_run(const int16_t *v, int k, ccd_enc_run *r, uint32_t *cw, int16_t *ex) {
     int mn = 0;
     if (k > 0) {
         mn = 32767;
@@ -434,7 +409,7 @@ __attribute__((target("avx512f,avx512bw"))) static inline unsigned pk_max16u(__m
  * alone cost as much as the best so far: e(w) only grows below it, so nothing there can win or
  * tie; going down, `<=` hands a tie to the smaller w, as the canonical choice wants. */
 __attribute__((target("avx512f,avx512bw,avx512vl,avx512vbmi2,bmi2"))) static uint32_t pk_pack_run_vec(
-    const int16_t *v, int k, pk_run_t *r, uint32_t *cw, int16_t *ex, uint16_t *rb) {
+    const int16_t *v, int k, ccd_enc_run *r, uint32_t *cw, int16_t *ex, uint16_t *rb) {
     r->base = 0;
     r->w = 0;
     r->n_exc = 0;
@@ -564,8 +539,8 @@ static size_t pk_pass2(int32_t n_pix, int32_t n_obs, const int16_t *spectra, con
                        uint8_t *q4, size_t rowb, const uint16_t *pal, int npal, const uint8_t *lut, uint16_t drop,
                        uint16_t strict, int nt, int *miss_out, int *bad_out) {
     const size_t plane = (size_t)n_pix * (size_t)n_obs;
-    pk_run_t *runs = (pk_run_t *)(q4 + up((size_t)n_pix * rowb, 16));
-    uint32_t *codes = (uint32_t *)(runs + 7 * (size_t)n_pix);
+    ccd_enc_run *runs = (ccd_enc_run *)ccd_enc_body(sec, n_pix, n_obs);
+    uint32_t *codes = (uint32_t *)ccd_enc_codes(sec, n_pix, n_obs);
     const int vec = have_vbmi2();
     const int pb = enc_block();
     const int mw = n_obs / 32 + 2;
@@ -582,7 +557,7 @@ static size_t pk_pass2(int32_t n_pix, int32_t n_obs, const int16_t *spectra, con
         uint32_t *cw = (uint32_t *)malloc(4 * ((size_t)pb * 7 * rw + 32));             /* (+ the vector packer's slack) */
         int16_t *ex = (int16_t *)malloc(2 * ((size_t)pb * 7 * (size_t)n_obs + 64));
         uint16_t *rb = (uint16_t *)malloc(2 * ((size_t)n_obs + 128));
-        pk_run_t *rs = (pk_run_t *)malloc(sizeof(pk_run_t) * 7 * (size_t)pb);
+        ccd_enc_run *rs = (ccd_enc_run *)malloc(sizeof(ccd_enc_run) * 7 * (size_t)pb);
         const int ok = vals && keep && km && cw && ex && rs && rb;
 #pragma omp for schedule(static, 1) ordered
         for (int32_t p0 = 0; p0 < n_pix; p0 += pb) {
@@ -597,7 +572,7 @@ static size_t pk_pass2(int32_t n_pix, int32_t n_obs, const int16_t *spectra, con
                     pk_qa_scalar(q, n_obs, lut, drop, strict, q4 + (size_t)p * rowb, keep, strictm);
                 for (int b = 0; b < 7; ++b) {
                     const int16_t *src = spectra + (size_t)b * plane + (size_t)p * n_obs;
-                    pk_run_t *r = rs + 7 * (size_t)(p - p0) + b;
+                    ccd_enc_run *r = rs + 7 * (size_t)(p - p0) + b;
                     uint32_t nw;
 #if defined(__x86_64__)
                     if (vec) {
@@ -645,7 +620,7 @@ static size_t pk_pass2(int32_t n_pix, int32_t n_obs, const int16_t *spectra, con
                 rs[i].code_word += (uint32_t)my_cw;
                 rs[i].exc_off += (uint32_t)my_ex;
             }
-            memcpy(runs + 7 * (size_t)p0, rs, sizeof(pk_run_t) * 7 * (size_t)(pe - p0));
+            memcpy(runs + 7 * (size_t)p0, rs, sizeof(ccd_enc_run) * 7 * (size_t)(pe - p0));
 #if defined(__x86_64__)
             if (vec && bw) pk_stream_out(codes + my_cw, cw, bw);
             else
@@ -674,14 +649,13 @@ static size_t pk_pass2(int32_t n_pix, int32_t n_obs, const int16_t *spectra, con
         return 1;  /* (any nonzero value: the caller looks at the flags first) */
     }
     /* the pad word and the padding of the codes part, then the exceptions */
-    const size_t cbytes = up(4 * ((size_t)g_cw + 1), 16);
-    memset(codes + g_cw, 0, cbytes - 4 * (size_t)g_cw);
-    int16_t *exc = (int16_t *)((uint8_t *)codes + cbytes);
-    if (g_ex) memcpy(exc, gex, 2 * (size_t)g_ex);
+    memset(codes + g_cw, 0, (size_t)ccd_enc_codes_bytes((int64_t)g_cw) - 4 * (size_t)g_cw);
+    if (g_ex) memcpy((int16_t *)ccd_enc_exc(sec, n_pix, n_obs, (int64_t)g_cw), gex, 2 * (size_t)g_ex);
     free(gex);
-    *(int64_t *)(sec + 88) = (int64_t)g_cw;
-    *(int64_t *)(sec + 96) = (int64_t)g_ex;
-    return (size_t)((uint8_t *)exc + 2 * (size_t)g_ex - sec);
+    ccd_enc_hdr *h = (ccd_enc_hdr *)sec;
+    h->code_words = (int64_t)g_cw;
+    h->exc_total = (int64_t)g_ex;
+    return (size_t)ccd_enc_size_pack(n_pix, n_obs, (int64_t)g_cw, (int64_t)g_ex);
 }
 
 /* one chip into sec (room for the larger of its two modes); returns the section's bytes */
@@ -703,7 +677,8 @@ static size_t encode_chip(int32_t n_pix, int32_t n_obs, const int16_t *spectra, 
      * per pixel): such a chip is known to be encodable -- its full palette, its strict observations
      * -- before pass 2 writes anything, so that a chip that goes raw after all never had bytes
      * written behind the raw section the call returns */
-    const int pack_small = (flags & CCDGPU_ENC_PACK) && sec_mode2_bound(n_pix, n_obs) > sec_mode0(n_pix, n_obs);
+    const int pack_small =
+        (flags & CCDGPU_ENC_PACK) && ccd_enc_size_pack_bound(n_pix, n_obs) > ccd_enc_size_raw((int64_t)plane);
     size_t ret = 0;
     for (int full = vec1 && !pack_small ? 0 : 1; full < 2; ++full) {
         const int sample = full ? 1 : ENC_SAMPLE;
@@ -755,26 +730,25 @@ static size_t encode_chip(int32_t n_pix, int32_t n_obs, const int16_t *spectra, 
                             ++npal;
                         }
         }
-        int32_t *h = (int32_t *)sec;
-        memset(sec, 0, ENC_HDR);
-        h[1] = n_pix;
-        h[2] = n_obs;
-        int64_t *h64 = (int64_t *)(sec + 48);
-        h64[1] = data_off;
-        h64[3] = pix_base;
+        ccd_enc_hdr *h = (ccd_enc_hdr *)sec;
+        memset(h, 0, sizeof *h);
+        h->n_pix = n_pix;
+        h->n_obs = n_obs;
+        h->data_off = data_off;
+        h->pix_base = pix_base;
         if (bad || npal > 16) {
             ret = encode_raw(n_pix, n_obs, spectra, qa, sec, nt);
             break;
         }
-        h[0] = 1;
-        h[3] = npal;
-        *(uint32_t *)(sec + 80) = drop;  /* the decoder's keep test */
-        uint16_t *pal = (uint16_t *)(sec + 16);
+        h->mode = CCD_ENC_MODE_COLS;
+        h->n_pal = npal;
+        h->drop_bits = drop;  /* the decoder's keep test */
+        uint16_t *pal = h->pal;
         for (int j = 0; j < npal; ++j) {
             pal[j] = palv[j];
             lut[palv[j]] = (uint8_t)j;
         }
-        uint32_t *koff = (uint32_t *)(sec + ENC_HDR);
+        uint32_t *koff = (uint32_t *)ccd_enc_koff(sec);
         uint64_t tot = 0;
         for (int32_t p = 0; p < n_pix; ++p) {
             koff[p] = (uint32_t)tot;
@@ -782,14 +756,14 @@ static size_t encode_chip(int32_t n_pix, int32_t n_obs, const int16_t *spectra, 
         }
         koff[n_pix] = (uint32_t)tot;
         /* padding after the offsets and after the code rows: deterministic bytes */
-        memset(koff + n_pix + 1, 0, up(4 * ((size_t)n_pix + 1), 16) - 4 * ((size_t)n_pix + 1));
-        const size_t bstride = up((size_t)tot, 8);
-        h64[0] = (int64_t)tot;
-        h64[2] = (int64_t)bstride;
-        uint8_t *q4 = sec + ENC_HDR + up(4 * ((size_t)n_pix + 1), 16);
-        const size_t rowb = (size_t)(n_obs + 1) / 2;
-        int16_t *bands = (int16_t *)(q4 + up((size_t)n_pix * rowb, 16));
-        memset(q4 + (size_t)n_pix * rowb, 0, up((size_t)n_pix * rowb, 16) - (size_t)n_pix * rowb);
+        memset(koff + n_pix + 1, 0, (size_t)ccd_enc_koff_bytes(n_pix) - 4 * ((size_t)n_pix + 1));
+        const size_t bstride = (size_t)ccd_enc_band_stride((int64_t)tot);
+        h->kept = (int64_t)tot;
+        h->band_stride = (int64_t)bstride;
+        uint8_t *q4 = (uint8_t *)ccd_enc_q4(sec, n_pix);
+        const size_t rowb = (size_t)ccd_enc_row_bytes(n_obs);
+        int16_t *bands = (int16_t *)ccd_enc_body(sec, n_pix, n_obs);
+        memset(q4 + (size_t)n_pix * rowb, 0, (size_t)ccd_enc_q4_bytes(n_pix, n_obs) - (size_t)n_pix * rowb);
         if (flags & CCDGPU_ENC_PACK) {  /* mode 2: the band runs bit-packed instead of the band columns */
             int pmiss = 0, pbad = 0;
             if (pack_small && strict) {
@@ -804,8 +778,8 @@ static size_t encode_chip(int32_t n_pix, int32_t n_obs, const int16_t *spectra, 
                     break;
                 }
             }
-            h[0] = 2;
-            h64[2] = 0;
+            h->mode = CCD_ENC_MODE_PACK;
+            h->band_stride = 0;
             const size_t sz = pk_pass2(n_pix, n_obs, spectra, qa, sec, q4, rowb, pal, npal, lut, drop, strict, nt,
                                        &pmiss, &pbad);
             if (sz && pmiss && !full) continue;
@@ -889,7 +863,7 @@ static size_t encode_chip(int32_t n_pix, int32_t n_obs, const int16_t *spectra, 
         }
         for (int b = 0; b < 7; ++b)  /* band padding: deterministic bytes */
             memset(bands + (size_t)b * bstride + tot, 0, 2 * (bstride - (size_t)tot));
-        ret = sec_mode1(n_pix, n_obs, (int64_t)tot);
+        ret = (size_t)ccd_enc_size_cols(n_pix, n_obs, (int64_t)bstride);
         break;
     }
     free(st);
@@ -912,9 +886,8 @@ int64_t ccdgpu_encode_chips_flags(int32_t n_chips, const int32_t *n_pix, const i
     if ((strict_bits & ~drop_bits) != 0) return -1;  /* a strict observation is a dropped one */
     const int64_t need = ccdgpu_encoded_bound_flags(n_chips, n_pix, n_obs, flags);
     if (need < 0 || out_cap < need) return -2;
-    int64_t *tab = (int64_t *)out;
-    tab[0] = n_chips;
-    int64_t *off = tab + 1, *pix = tab + 2 + n_chips;
+    *(int64_t *)out = n_chips;  /* the chip table: n_chips, chip_off, chip_pix */
+    int64_t *off = (int64_t *)ccd_enc_chip_off(out), *pix = (int64_t *)ccd_enc_chip_pix(out, n_chips);
     int32_t maxp = 0;
     for (int32_t c = 0; c < n_chips; ++c) {
         if (n_pix[c] <= 0 || n_obs[c] <= 0 || !spectra[c] || !qa[c]) return -1;
@@ -922,8 +895,8 @@ int64_t ccdgpu_encode_chips_flags(int32_t n_chips, const int32_t *n_pix, const i
     }
     uint32_t *kept = (uint32_t *)malloc(4 * (size_t)maxp);
     if (!kept) return -3;
-    size_t pos = table_bytes(n_chips);
-    memset(out + 8 + 16 * ((size_t)n_chips + 1), 0, pos - (8 + 16 * ((size_t)n_chips + 1)));  /* table padding */
+    size_t pos = (size_t)ccd_enc_table_bytes(n_chips);
+    memset(out + ccd_enc_table_used(n_chips), 0, pos - (size_t)ccd_enc_table_used(n_chips));  /* table padding */
     int64_t pbase = 0, dbase = 0;
     for (int32_t c = 0; c < n_chips; ++c) {
         off[c] = (int64_t)pos;
@@ -934,8 +907,9 @@ int64_t ccdgpu_encode_chips_flags(int32_t n_chips, const int32_t *n_pix, const i
             free(kept);
             return -3;
         }
-        memset(out + pos + sz, 0, up(sz, ENC_ALIGN) - sz);  /* section padding */
-        pos += up(sz, ENC_ALIGN);
+        const size_t szp = (size_t)ccd_enc_up_align((int64_t)sz);
+        memset(out + pos + sz, 0, szp - sz);  /* section padding */
+        pos += szp;
         pbase += n_pix[c];
         dbase += (int64_t)n_pix[c] * n_obs[c];
     }

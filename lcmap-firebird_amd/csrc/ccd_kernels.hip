@@ -31,6 +31,7 @@
 #include <stdint.h>
 
 #include "ccd_device.h"
+#include "ccd_enc_layout.h"
 
 namespace {
 
@@ -3664,7 +3665,7 @@ __device__ __forceinline__ void standard_procedure(Px &P, int proc) {
 // ------------------------------------------------------------------ qa.py filters + compaction
 // A pixel's inputs are read where they lie: the standard band-major layout (a plain upload, the
 // chipmunk decoder), a raw section of a transport-encoded batch (the same layout at the section's
-// own base pointers), or an encoded section (include/ccdgpu.h; ccd_encode.c) -- QA as 4-bit
+// own base pointers), or an encoded section (include/ccdgpu.h; ccd_enc_layout.h) -- QA as 4-bit
 // palette codes, band values sent only for observations without a drop bit, compacted per pixel.
 // An encoded pixel is read in place, so the upload needs no decode pass (the standalone decoder
 // ccd_decode_enc in ccd_pack.hip is the same mapping): pass 1 walks the code row in input order
@@ -3688,27 +3689,25 @@ __device__ __forceinline__ int px_setup(Px &P, int chip, int pix) {
     unsigned drop = 0u;
     bool enc = false;
     if (A.enc) {
-        const unsigned char *sec = A.enc + reinterpret_cast<const int64_t *>(A.enc)[1 + chip];
-        const int32_t *h = reinterpret_cast<const int32_t *>(sec);
-        const int64_t cpix = h[1];
+        const unsigned char *sec = A.enc + ccd_enc_chip_off(A.enc)[chip];
+        const ccd_enc_hdr *h = reinterpret_cast<const ccd_enc_hdr *>(sec);
+        const int64_t cpix = h->n_pix;
         const int64_t plane = cpix * n;
-        if (h[0] == 0) {
-            qa = reinterpret_cast<const uint16_t *>(sec + 128) + (size_t)pix * n;
-            sp = reinterpret_cast<const int16_t *>(sec + 128 + ((2 * plane + 15) & ~(int64_t)15)) + (size_t)pix * n;
+        if (h->mode == CCD_ENC_MODE_RAW) {
+            qa = reinterpret_cast<const uint16_t *>(ccd_enc_raw_qa(sec)) + (size_t)pix * n;
+            sp = reinterpret_cast<const int16_t *>(ccd_enc_raw_spectra(sec, plane)) + (size_t)pix * n;
             bstride = (size_t)plane;
         } else {
             enc = true;
-            bstride = (size_t)reinterpret_cast<const int64_t *>(sec + 48)[2];
-            const uint32_t *koff = reinterpret_cast<const uint32_t *>(sec + 128);
-            const unsigned char *q4 = sec + 128 + ((4 * (cpix + 1) + 15) & ~(int64_t)15);
-            const int64_t rowb = (n + 1) / 2;
-            codes = q4 + (size_t)pix * rowb;
+            bstride = (size_t)h->band_stride;
+            const uint32_t *koff = reinterpret_cast<const uint32_t *>(ccd_enc_koff(sec));
+            codes = ccd_enc_q4(sec, cpix) + (size_t)pix * ccd_enc_row_bytes(n);
             const uint32_t k0 = koff[pix];
             kcount = (int)(koff[pix + 1] - k0);
-            sp = reinterpret_cast<const int16_t *>(q4 + ((cpix * rowb + 15) & ~(int64_t)15)) + k0;
+            sp = reinterpret_cast<const int16_t *>(ccd_enc_body(sec, cpix, n)) + k0;
             qa = nullptr;
-            drop = *reinterpret_cast<const uint32_t *>(sec + 80);
-            if (l < 16) L->epal[l] = reinterpret_cast<const uint16_t *>(sec + 16)[l];
+            drop = h->drop_bits;
+            if (l < 16) L->epal[l] = h->pal[l];
             wsync();
         }
     } else {

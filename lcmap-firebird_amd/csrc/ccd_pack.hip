@@ -24,6 +24,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ccd_enc_layout.h"
+
 namespace {
 
 constexpr int OBS_T = 128;  // observations per tile
@@ -153,41 +155,35 @@ __global__ __launch_bounds__(256, 6) void ccd_unpack_b64(const unsigned char *__
     if (bad) atomicOr(err, 1ull);
 }
 
-// ---- transport-encoded batches (ccd_encode.c; layout in include/ccdgpu.h) -> the standard
+// ---- transport-encoded batches (ccd_encode.c; layout in include/ccdgpu.h, every offset through
+// ccd_enc_layout.h) -> the standard
 // band-major spectra [7][n_pix][n_obs] and QA [n_pix][n_obs] of every chip.  One wave per
 // pixel, lane = observation: the 4-bit QA code through the chip's palette, the kept
 // observations' (no drop bit) rank by ballot / mbcnt, band values gathered from the compacted
 // band columns (consecutive ranks: coalesced) and -9999 written for the dropped ones.  Byte
 // work at HBM speed: ~13 B read and 16 B written per observation.
-constexpr int ENC_HDR = 128;
-__device__ __forceinline__ int64_t up16(int64_t x) { return (x + 15) & ~(int64_t)15; }
-
+// The start (chip lookup, header fields, the copy of a raw section's pixel) is the same in
+// ccd_decode_pack and stays written out in both: as a shared inlined helper it compiles to
+// different instructions than this (a helper is optimised on its own before it is inlined).
 __global__ __launch_bounds__(256) void ccd_decode_enc(const unsigned char *__restrict__ enc, int64_t total_pix,
                                                        int16_t *__restrict__ spectra, uint16_t *__restrict__ qa) {
     const int64_t pix = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (pix >= total_pix) return;
     const int l = threadIdx.x & 63;
-    const int64_t *tab = reinterpret_cast<const int64_t *>(enc);
-    const int64_t nc = tab[0];
-    const int64_t *off = tab + 1, *pixo = tab + 2 + nc;
-    int64_t lo = 0, hi = nc - 1;  // the pixel's chip (wave-uniform binary search)
-    while (lo < hi) {
-        const int64_t mid = (lo + hi + 1) >> 1;
-        if (pixo[mid] <= pix) lo = mid;
-        else hi = mid - 1;
-    }
+    const int64_t nc = ccd_enc_n_chips(enc);
+    const int64_t *off = ccd_enc_chip_off(enc), *pixo = ccd_enc_chip_pix(enc, nc);
+    CCD_ENC_FIND_CHIP(lo, pixo, nc, pix);  // the pixel's chip (wave-uniform)
     const unsigned char *sec = enc + off[lo];
-    const int32_t *h = reinterpret_cast<const int32_t *>(sec);
-    const int mode = h[0], n_pix = h[1], n_obs = h[2];
-    const int64_t *h64 = reinterpret_cast<const int64_t *>(sec + 48);
-    const int64_t data_off = h64[1], bstride = h64[2];
+    const ccd_enc_hdr *h = reinterpret_cast<const ccd_enc_hdr *>(sec);
+    const int mode = h->mode, n_pix = h->n_pix, n_obs = h->n_obs;
+    const int64_t data_off = h->data_off, bstride = h->band_stride;
     const int64_t p = pix - pixo[lo];
     const int64_t plane = (int64_t)n_pix * n_obs;
     int16_t *sp = spectra + 7 * data_off + p * n_obs;
     uint16_t *qo = qa + data_off + p * n_obs;
-    if (mode == 0) {
-        const uint16_t *rq = reinterpret_cast<const uint16_t *>(sec + ENC_HDR) + p * n_obs;
-        const int16_t *rs = reinterpret_cast<const int16_t *>(sec + ENC_HDR + up16(2 * plane)) + p * n_obs;
+    if (mode == CCD_ENC_MODE_RAW) {
+        const uint16_t *rq = reinterpret_cast<const uint16_t *>(ccd_enc_raw_qa(sec)) + p * n_obs;
+        const int16_t *rs = reinterpret_cast<const int16_t *>(ccd_enc_raw_spectra(sec, plane)) + p * n_obs;
         for (int i = l; i < n_obs; i += 64) {
             qo[i] = rq[i];
 #pragma unroll
@@ -197,16 +193,14 @@ __global__ __launch_bounds__(256) void ccd_decode_enc(const unsigned char *__res
     }
     // the palette in registers (lane j < 16 holds entry j): a code is looked up with one lane
     // permute instead of a dependent global load
-    const uint16_t palr = l < 16 ? reinterpret_cast<const uint16_t *>(sec + 16)[l] : (uint16_t)0;
-    const unsigned drop = *reinterpret_cast<const uint32_t *>(sec + 80);  // QA bits whose bands were not sent
-    const uint32_t *koff = reinterpret_cast<const uint32_t *>(sec + ENC_HDR);
-    const unsigned char *q4 = sec + ENC_HDR + up16(4 * ((int64_t)n_pix + 1));
-    const int64_t rowb = (n_obs + 1) / 2;
-    const int16_t *bands = reinterpret_cast<const int16_t *>(q4 + up16((int64_t)n_pix * rowb)) + koff[p];
+    const uint16_t palr = l < 16 ? h->pal[l] : (uint16_t)0;
+    const unsigned drop = h->drop_bits;  // QA bits whose bands were not sent
+    const uint32_t *koff = reinterpret_cast<const uint32_t *>(ccd_enc_koff(sec));
+    const int16_t *bands = reinterpret_cast<const int16_t *>(ccd_enc_body(sec, n_pix, n_obs)) + koff[p];
     // the pixel's kept run (the host checked the table); a code row that claims more kept
     // observations than the run holds reads no further than the run (its excess gets -9999)
     const int kcount = (int)(koff[p + 1] - koff[p]);
-    const unsigned char *qr = q4 + p * rowb;
+    const unsigned char *qr = ccd_enc_q4(sec, n_pix) + p * ccd_enc_row_bytes(n_obs);
     int carry = 0;
     // four 64-observation chunks per round: their code bytes load together, then their ranks,
     // then all 28 band loads go out before the first store (latency once per round, not per chunk)
@@ -263,39 +257,25 @@ __global__ __launch_bounds__(256) void ccd_decode_enc(const unsigned char *__res
 // check (ccdgpu_encoded_check) has tied every run's code_word / exc_off to the prefix sums of
 // ceil(k w / 32) and n_exc, so rank < k and erank < n_exc keep every load inside the section
 // whatever the code bits say; a lane outside them gets -9999.
-struct PackRun {
-    int16_t base;
-    uint16_t w;
-    uint32_t code_word, exc_off, n_exc;
-};
-static_assert(sizeof(PackRun) == 16, "run descriptor layout");
-
 __global__ __launch_bounds__(256) void ccd_decode_pack(const unsigned char *__restrict__ enc, int64_t total_pix,
                                                         int16_t *__restrict__ spectra, uint16_t *__restrict__ qa) {
     const int64_t pix = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (pix >= total_pix) return;
     const int l = threadIdx.x & 63;
-    const int64_t *tab = reinterpret_cast<const int64_t *>(enc);
-    const int64_t nc = tab[0];
-    const int64_t *off = tab + 1, *pixo = tab + 2 + nc;
-    int64_t lo = 0, hi = nc - 1;  // the pixel's chip (wave-uniform binary search)
-    while (lo < hi) {
-        const int64_t mid = (lo + hi + 1) >> 1;
-        if (pixo[mid] <= pix) lo = mid;
-        else hi = mid - 1;
-    }
+    const int64_t nc = ccd_enc_n_chips(enc);
+    const int64_t *off = ccd_enc_chip_off(enc), *pixo = ccd_enc_chip_pix(enc, nc);
+    CCD_ENC_FIND_CHIP(lo, pixo, nc, pix);  // the pixel's chip (wave-uniform)
     const unsigned char *sec = enc + off[lo];
-    const int32_t *h = reinterpret_cast<const int32_t *>(sec);
-    const int mode = h[0], n_pix = h[1], n_obs = h[2];
-    const int64_t *h64 = reinterpret_cast<const int64_t *>(sec + 48);
-    const int64_t data_off = h64[1];
+    const ccd_enc_hdr *h = reinterpret_cast<const ccd_enc_hdr *>(sec);
+    const int mode = h->mode, n_pix = h->n_pix, n_obs = h->n_obs;
+    const int64_t data_off = h->data_off;
     const int64_t p = pix - pixo[lo];
     const int64_t plane = (int64_t)n_pix * n_obs;
     int16_t *sp = spectra + 7 * data_off + p * n_obs;
     uint16_t *qo = qa + data_off + p * n_obs;
-    if (mode != 2) {  // raw (the host check admits only modes 0 and 2 here)
-        const uint16_t *rq = reinterpret_cast<const uint16_t *>(sec + ENC_HDR) + p * n_obs;
-        const int16_t *rs = reinterpret_cast<const int16_t *>(sec + ENC_HDR + up16(2 * plane)) + p * n_obs;
+    if (mode != CCD_ENC_MODE_PACK) {  // raw (the host check admits only modes 0 and 2 here)
+        const uint16_t *rq = reinterpret_cast<const uint16_t *>(ccd_enc_raw_qa(sec)) + p * n_obs;
+        const int16_t *rs = reinterpret_cast<const int16_t *>(ccd_enc_raw_spectra(sec, plane)) + p * n_obs;
         for (int i = l; i < n_obs; i += 64) {
             qo[i] = rq[i];
 #pragma unroll
@@ -303,20 +283,17 @@ __global__ __launch_bounds__(256) void ccd_decode_pack(const unsigned char *__re
         }
         return;
     }
-    const uint16_t palr = l < 16 ? reinterpret_cast<const uint16_t *>(sec + 16)[l] : (uint16_t)0;
-    const unsigned drop = *reinterpret_cast<const uint32_t *>(sec + 80);
-    const int64_t code_words = h64[5];  // byte 88
-    const uint32_t *koff = reinterpret_cast<const uint32_t *>(sec + ENC_HDR);
-    const unsigned char *q4 = sec + ENC_HDR + up16(4 * ((int64_t)n_pix + 1));
-    const int64_t rowb = (n_obs + 1) / 2;
-    const PackRun *runs = reinterpret_cast<const PackRun *>(q4 + up16((int64_t)n_pix * rowb));
-    const uint32_t *codes = reinterpret_cast<const uint32_t *>(runs + 7 * (int64_t)n_pix);
-    const int16_t *exc = reinterpret_cast<const int16_t *>(reinterpret_cast<const unsigned char *>(codes) +
-                                                           up16(4 * (code_words + 1)));
+    const uint16_t palr = l < 16 ? h->pal[l] : (uint16_t)0;
+    const unsigned drop = h->drop_bits;
+    const int64_t code_words = h->code_words;
+    const uint32_t *koff = reinterpret_cast<const uint32_t *>(ccd_enc_koff(sec));
+    const ccd_enc_run *runs = reinterpret_cast<const ccd_enc_run *>(ccd_enc_body(sec, n_pix, n_obs));
+    const uint32_t *codes = reinterpret_cast<const uint32_t *>(ccd_enc_codes(sec, n_pix, n_obs));
+    const int16_t *exc = reinterpret_cast<const int16_t *>(ccd_enc_exc(sec, n_pix, n_obs, code_words));
     const int kcount = (int)(koff[p + 1] - koff[p]);
-    const unsigned char *qr = q4 + p * rowb;
-    // the pixel's seven descriptors (112 contiguous bytes, the same for every lane)
-    PackRun run[7];
+    const unsigned char *qr = ccd_enc_q4(sec, n_pix) + p * ccd_enc_row_bytes(n_obs);
+    // the pixel's seven descriptors (contiguous, the same for every lane)
+    ccd_enc_run run[7];
 #pragma unroll
     for (int b = 0; b < 7; ++b) {
         const uint4 d = reinterpret_cast<const uint4 *>(runs + 7 * p)[b];

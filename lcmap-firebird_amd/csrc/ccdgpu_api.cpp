@@ -24,6 +24,7 @@
 
 #include "../../include/ccdgpu.h"
 #include "ccd_device.h"
+#include "ccd_enc_layout.h"
 
 namespace {
 
@@ -751,87 +752,87 @@ int ccdgpu_stage_slot_chips(ccdgpu_ctx *c, int32_t slot, const ccdgpu_params *pa
     return 0;
 }
 
-// ccdgpu_encoded_check; *packed: the batch holds a mode 2 section (it goes to ccd_decode_pack)
+// "encoded batch: chip N" + what is wrong with it
+static int enc_fail(int32_t chip, const std::string &what) {
+    return fail(CCDGPU_EINVAL, "encoded batch: chip " + std::to_string(chip) + what);
+}
+
+// the kept-offset table of a mode 1 or 2 section: a run of at most n_obs per pixel, ending at kept
+static int enc_check_koff(int32_t chip, const uint32_t *koff, int64_t n_pix, int64_t n_obs, int64_t kept) {
+    if (koff[0] != 0 || (int64_t)koff[n_pix] != kept) return enc_fail(chip, " kept-offset table does not end at kept");
+    for (int64_t q = 0; q < n_pix; ++q)
+        if (koff[q + 1] < koff[q] || (int64_t)(koff[q + 1] - koff[q]) > n_obs)
+            return enc_fail(chip, " kept-offset table is not a run per pixel");
+    return 0;
+}
+
+// ccdgpu_encoded_check (layout: ccd_enc_layout.h); *packed: the batch holds a mode 2 section (it
+// goes to ccd_decode_pack)
 static int encoded_check(int32_t n_chips, const int32_t *n_pix, const int32_t *n_obs, const uint8_t *enc,
                          int64_t enc_bytes, bool *packed) {
     *packed = false;
     bool mode1 = false;
     if (!enc || !n_pix || !n_obs || n_chips <= 0) return fail(CCDGPU_EINVAL, "NULL or empty encoded batch");
     // the encoded batch must describe exactly these chips (the decoder trusts its headers)
-    const int64_t *tab = reinterpret_cast<const int64_t *>(enc);
-    if (enc_bytes < (int64_t)(8 * (2 * (int64_t)n_chips + 3)) || tab[0] != n_chips)
+    if (enc_bytes < ccd_enc_table_used(n_chips) || ccd_enc_n_chips(enc) != n_chips)
         return fail(CCDGPU_EINVAL, "encoded batch: chip table does not match n_chips");
-    const int64_t *off = tab + 1, *pixo = tab + 2 + n_chips;
+    const int64_t *off = ccd_enc_chip_off(enc), *pixo = ccd_enc_chip_pix(enc, n_chips);
     if (off[n_chips] > enc_bytes) return fail(CCDGPU_EINVAL, "encoded batch: longer than enc_bytes");
     int64_t pb = 0, db = 0;
     for (int32_t k = 0; k < n_chips; ++k) {
         if (n_pix[k] <= 0 || n_obs[k] <= 0 || n_obs[k] > CCDGPU_MAX_OBS)
-            return fail(CCDGPU_EINVAL, "encoded batch: chip " + std::to_string(k) + " has no pixels / observations");
-        if (off[k] < 0 || off[k] + 128 > off[k + 1] || pixo[k] != pb)
+            return enc_fail(k, " has no pixels / observations");
+        if (off[k] < 0 || off[k] + CCD_ENC_HDR > off[k + 1] || pixo[k] != pb)
             return fail(CCDGPU_EINVAL, "encoded batch: bad chip table entry " + std::to_string(k));
-        const int32_t *h = reinterpret_cast<const int32_t *>(enc + off[k]);
-        const int64_t *h64 = reinterpret_cast<const int64_t *>(enc + off[k] + 48);
-        if ((h[0] != 0 && h[0] != 1 && h[0] != 2) || h[1] != n_pix[k] || h[2] != n_obs[k] || h64[1] != db ||
-            (h[0] != 0 && (h[3] < 1 || h[3] > 16)))
-            return fail(CCDGPU_EINVAL, "encoded batch: chip " + std::to_string(k) + " header does not match its shape");
+        const uint8_t *sec = enc + off[k];
+        const ccd_enc_hdr *h = reinterpret_cast<const ccd_enc_hdr *>(sec);
+        if ((h->mode != CCD_ENC_MODE_RAW && h->mode != CCD_ENC_MODE_COLS && h->mode != CCD_ENC_MODE_PACK) ||
+            h->n_pix != n_pix[k] || h->n_obs != n_obs[k] || h->data_off != db ||
+            (h->mode != CCD_ENC_MODE_RAW && (h->n_pal < 1 || h->n_pal > 16)))
+            return enc_fail(k, " header does not match its shape");
         // the section holds everything its mode's layout addresses (the decoder trusts it)
-        const int64_t np_ = n_pix[k], no_ = n_obs[k], plane = np_ * no_, sec = off[k + 1] - off[k];
-        auto up_ = [](int64_t x, int64_t a) { return (x + a - 1) / a * a; };
-        if (h[0] == 0) {
-            if (sec < 128 + up_(2 * plane, 16) + 14 * plane)
-                return fail(CCDGPU_EINVAL, "encoded batch: chip " + std::to_string(k) + " raw section is truncated");
-        } else if (h[0] == 2) {
+        const int64_t np_ = n_pix[k], plane = np_ * n_obs[k], sec_bytes = off[k + 1] - off[k];
+        const int32_t no_ = n_obs[k];
+        const uint32_t *koff = reinterpret_cast<const uint32_t *>(ccd_enc_koff(sec));
+        int rc;
+        if (h->mode == CCD_ENC_MODE_RAW) {
+            if (sec_bytes < ccd_enc_size_raw(plane)) return enc_fail(k, " raw section is truncated");
+        } else if (h->mode == CCD_ENC_MODE_PACK) {
             // bit-packed runs: the kept table as in mode 1, then every run's descriptor against the
             // prefix sums of its code words (ceil(k w / 32)) and exceptions, the totals against the
             // header, and the section long enough for all five parts and the pad word -- after
             // this no code bit can send the decoder outside the section
             *packed = true;
-            const std::string chip = "encoded batch: chip " + std::to_string(k);
-            const int64_t kept = h64[0], code_words = h64[5], exc_total = h64[6];
-            const int64_t runs_at = 128 + up_(4 * (np_ + 1), 16) + up_(np_ * ((no_ + 1) / 2), 16);
-            const int64_t codes_at = runs_at + 112 * np_;
-            if (kept < 0 || kept > plane || h64[2] != 0 || code_words < 0 || exc_total < 0 ||
-                code_words > 4 * plane + 8 * np_ || exc_total > 7 * plane || sec < codes_at)
-                return fail(CCDGPU_EINVAL, chip + " packed header does not fit its section");
-            const uint32_t *koff = reinterpret_cast<const uint32_t *>(enc + off[k] + 128);
-            if (koff[0] != 0 || (int64_t)koff[np_] != kept)
-                return fail(CCDGPU_EINVAL, chip + " kept-offset table does not end at kept");
-            for (int64_t q = 0; q < np_; ++q)
-                if (koff[q + 1] < koff[q] || (int64_t)(koff[q + 1] - koff[q]) > no_)
-                    return fail(CCDGPU_EINVAL, chip + " kept-offset table is not a run per pixel");
-            const uint8_t *runs = enc + off[k] + runs_at;
+            const int64_t kept = h->kept, code_words = h->code_words, exc_total = h->exc_total;
+            if (kept < 0 || kept > plane || h->band_stride != 0 || code_words < 0 || exc_total < 0 ||
+                code_words > 4 * plane + 8 * np_ || exc_total > 7 * plane ||
+                sec_bytes < ccd_enc_size_pack_fixed(np_, no_))
+                return enc_fail(k, " packed header does not fit its section");
+            if ((rc = enc_check_koff(k, koff, np_, no_, kept))) return rc;
+            const ccd_enc_run *runs = reinterpret_cast<const ccd_enc_run *>(ccd_enc_body(sec, np_, no_));
             int64_t cw = 0, ex = 0;
-            for (int64_t r = 0; r < 7 * np_; ++r) {
-                const uint8_t *d = runs + 16 * r;
-                uint16_t w;
-                uint32_t f[3];
-                std::memcpy(&w, d + 2, 2);
-                std::memcpy(f, d + 4, 12);
-                const int64_t kk = (int64_t)(koff[r / 7 + 1] - koff[r / 7]);
-                if (w > 16) return fail(CCDGPU_EINVAL, chip + " run " + std::to_string(r) + " has a width above 16");
-                if ((int64_t)f[0] != cw || (int64_t)f[1] != ex)
-                    return fail(CCDGPU_EINVAL, chip + " run " + std::to_string(r) + " does not start at the prefix sums");
-                if ((int64_t)f[2] > kk)
-                    return fail(CCDGPU_EINVAL, chip + " run " + std::to_string(r) + " has more exceptions than values");
-                cw += (kk * w + 31) / 32;
-                ex += f[2];
+            for (int64_t r = 0; r < CCD_ENC_BANDS * np_; ++r) {
+                const ccd_enc_run &d = runs[r];
+                const int64_t kk = (int64_t)(koff[r / CCD_ENC_BANDS + 1] - koff[r / CCD_ENC_BANDS]);
+                if (d.w > 16) return enc_fail(k, " run " + std::to_string(r) + " has a width above 16");
+                if ((int64_t)d.code_word != cw || (int64_t)d.exc_off != ex)
+                    return enc_fail(k, " run " + std::to_string(r) + " does not start at the prefix sums");
+                if ((int64_t)d.n_exc > kk)
+                    return enc_fail(k, " run " + std::to_string(r) + " has more exceptions than values");
+                cw += (kk * d.w + 31) / 32;
+                ex += d.n_exc;
             }
             if (cw != code_words || ex != exc_total)
-                return fail(CCDGPU_EINVAL, chip + " run totals do not match code_words / exc_total");
-            if (sec < codes_at + up_(4 * (code_words + 1), 16) + 2 * exc_total)
-                return fail(CCDGPU_EINVAL, chip + " packed section is truncated");
+                return enc_fail(k, " run totals do not match code_words / exc_total");
+            if (sec_bytes < ccd_enc_size_pack(np_, no_, code_words, exc_total))
+                return enc_fail(k, " packed section is truncated");
         } else {
             mode1 = true;
-            const int64_t kept = h64[0], bstride = h64[2];
-            const int64_t bands_at = 128 + up_(4 * (np_ + 1), 16) + up_(np_ * ((no_ + 1) / 2), 16);
-            if (kept < 0 || kept > plane || bstride < kept || bstride % 8 != 0 || sec < bands_at + 14 * bstride)
-                return fail(CCDGPU_EINVAL, "encoded batch: chip " + std::to_string(k) + " band columns do not fit its section");
-            const uint32_t *koff = reinterpret_cast<const uint32_t *>(enc + off[k] + 128);
-            if (koff[0] != 0 || (int64_t)koff[np_] != kept)
-                return fail(CCDGPU_EINVAL, "encoded batch: chip " + std::to_string(k) + " kept-offset table does not end at kept");
-            for (int64_t q = 0; q < np_; ++q)
-                if (koff[q + 1] < koff[q] || (int64_t)(koff[q + 1] - koff[q]) > no_)
-                    return fail(CCDGPU_EINVAL, "encoded batch: chip " + std::to_string(k) + " kept-offset table is not a run per pixel");
+            const int64_t kept = h->kept, bstride = h->band_stride;
+            if (kept < 0 || kept > plane || bstride < kept || bstride % 8 != 0 ||
+                sec_bytes < ccd_enc_size_cols(np_, no_, bstride))
+                return enc_fail(k, " band columns do not fit its section");
+            if ((rc = enc_check_koff(k, koff, np_, no_, kept))) return rc;
         }
         pb += n_pix[k];
         db += (int64_t)n_pix[k] * n_obs[k];
@@ -864,7 +865,7 @@ int ccdgpu_stage_slot_encoded(ccdgpu_ctx *c, int32_t slot, const ccdgpu_params *
     // a batch with bit-packed sections is always decoded into the slot's standard buffers (the
     // detection kernel reads modes 0 and 1 in place, not mode 2)
     const bool decode = c->decode_enc || packed;
-    const int64_t *off = reinterpret_cast<const int64_t *>(enc) + 1;
+    const int64_t *off = ccd_enc_chip_off(enc);
     const int64_t pb = sh.total_pix();
     HIPCHK(hipSetDevice(c->device));
     const size_t tobs = (size_t)sh.total_obs(), tdata = (size_t)sh.total_data();

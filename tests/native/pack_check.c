@@ -2,8 +2,9 @@
  * include/ccdgpu.h): random small chips -- band runs of random spread, so every width from 0 to
  * 16 and runs with exceptions occur -- are encoded with ccdgpu_encode_chips_flags(CCDGPU_ENC_PACK)
  * at random thread counts into a buffer filled with a sentinel, decoded by the plain-C decoder
- * below, and compared with the inputs; every byte behind the returned count must still hold the
- * sentinel.  Built with -fsanitize=address,undefined and run by tests/test_encode_pack.py. */
+ * below (parts located through csrc/ccd_enc_layout.h, which the encoder source includes; the
+ * bit-by-bit decode is its own), and compared with the inputs; every byte behind the returned
+ * count must still hold the sentinel.  Built with -fsanitize=address,undefined and run by tests/test_encode_pack.py. */
 #include "../../lcmap-firebird_amd/csrc/ccd_encode.c"
 
 #include <stdio.h>
@@ -11,36 +12,31 @@
 static unsigned rs = 1;
 #define RND() (rs = rs * 1103515245u + 12345u, (rs >> 8))
 
-static int64_t up16(int64_t x) { return (x + 15) / 16 * 16; }
-
 /* one section into sp [7][n_pix][n_obs] and qa [n_pix][n_obs]; 0 on success */
 static int decode_section(const uint8_t *sec, int16_t *sp, uint16_t *qa) {
-    int32_t h[4];
-    int64_t h64[7];
-    uint32_t drop;
-    memcpy(h, sec, 16);
-    memcpy(h64, sec + 48, 56);
-    memcpy(&drop, sec + 80, 4);
-    const int64_t n_pix = h[1], n_obs = h[2], plane = n_pix * n_obs;
-    if (h[0] == 0) {
-        memcpy(qa, sec + ENC_HDR, 2 * (size_t)plane);
-        memcpy(sp, sec + ENC_HDR + up16(2 * plane), 14 * (size_t)plane);
+    ccd_enc_hdr h;
+    memcpy(&h, sec, sizeof h);
+    const uint32_t drop = h.drop_bits;
+    const int64_t n_pix = h.n_pix, n_obs = h.n_obs, plane = n_pix * n_obs;
+    if (h.mode == CCD_ENC_MODE_RAW) {
+        memcpy(qa, ccd_enc_raw_qa(sec), 2 * (size_t)plane);
+        memcpy(sp, ccd_enc_raw_spectra(sec, plane), 14 * (size_t)plane);
         return 0;
     }
-    if (h[0] != 2 || h64[2] != 0) return 1;
-    const uint16_t *pal = (const uint16_t *)(sec + 16);
-    const uint32_t *koff = (const uint32_t *)(sec + ENC_HDR);
-    const int64_t rowb = (n_obs + 1) / 2;
-    const uint8_t *q4 = sec + ENC_HDR + up16(4 * (n_pix + 1));
-    const pk_run_t *runs = (const pk_run_t *)(q4 + up16(n_pix * rowb));
-    const uint32_t *codes = (const uint32_t *)(runs + 7 * n_pix);
-    const int16_t *exc = (const int16_t *)((const uint8_t *)codes + up16(4 * (h64[5] + 1)));
-    if (codes[h64[5]] != 0) return 2; /* the pad word */
+    if (h.mode != CCD_ENC_MODE_PACK || h.band_stride != 0) return 1;
+    const uint16_t *pal = h.pal;
+    const uint32_t *koff = (const uint32_t *)ccd_enc_koff(sec);
+    const int64_t rowb = ccd_enc_row_bytes(h.n_obs);
+    const uint8_t *q4 = ccd_enc_q4(sec, n_pix);
+    const ccd_enc_run *runs = (const ccd_enc_run *)ccd_enc_body(sec, n_pix, h.n_obs);
+    const uint32_t *codes = (const uint32_t *)ccd_enc_codes(sec, n_pix, h.n_obs);
+    const int16_t *exc = (const int16_t *)ccd_enc_exc(sec, n_pix, h.n_obs, h.code_words);
+    if (codes[h.code_words] != 0) return 2; /* the pad word */
     for (int64_t p = 0; p < n_pix; ++p) {
         const int64_t k = (int64_t)koff[p + 1] - koff[p];
         for (int64_t i = 0; i < n_obs; ++i) qa[p * n_obs + i] = pal[(q4[p * rowb + i / 2] >> (4 * (i & 1))) & 15];
         for (int b = 0; b < 7; ++b) {
-            const pk_run_t *r = runs + 7 * p + b;
+            const ccd_enc_run *r = runs + 7 * p + b;
             if (r->w > 16 || r->n_exc > k) return 3;
             int64_t rank = 0, er = 0;
             for (int64_t i = 0; i < n_obs; ++i) {

@@ -213,6 +213,48 @@ def test_encoded_check_rejects_malformed_batches_on_the_host():
     corrupt(lambda b: b.buf[off[1] + 4:off[1] + 8].view(np.int32).__setitem__(0, 41))
 
 
+def test_encoded_check_section_sizes_are_exact_for_modes_1_and_0():
+    """The section sizes the checker asks for (the size functions of ccd_enc_layout.h, shared with
+    the encoder) against the layout written out here: a batch whose last section -- mode 1, then
+    raw -- ends exactly where its last part does passes, one 2 bytes shorter is rejected.  (Mode 2:
+    test_encode_pack.py, pack_util.exact_end and 'no pad word'.)"""
+    def up16(x):
+        return (x + 15) // 16 * 16
+
+    def cut_last_section(chips, mode, size):
+        e, _ = encode(chips, threads=2)
+        assert e.chip_modes()[-1] == mode
+        table = e.buf[8:8 * (e.n_chips + 2)].view(np.int64)  # chip_off[n_chips + 1]
+        assert table[-2] + size(e, int(table[-2])) <= table[-1]
+        for short, ok in ((0, True), (2, False)):
+            table[-1] = table[-2] + size(e, int(table[-2])) - short
+            if ok:
+                e.check()
+            else:
+                with pytest.raises(ccdgpu.CcdGpuError, match='encoded batch'):
+                    e.check()
+
+    def size_mode1(e, at):
+        n_pix, n_obs = int(e.n_pix[-1]), int(e.n_obs[-1])
+        band_stride = int(e.buf[at + 64:at + 72].view(np.int64)[0])
+        assert band_stride > 0
+        return 128 + up16(4 * (n_pix + 1)) + up16(n_pix * ((n_obs + 1) // 2)) + 14 * band_stride
+
+    def size_mode0(e, at):
+        plane = int(e.n_pix[-1]) * int(e.n_obs[-1])
+        return 128 + up16(2 * plane) + 14 * plane
+
+    cfg = synth.config(3)
+    cut_last_section([synth.chip(cfg, 0, 0, 64), synth.chip(cfg, 1, 0, 40)], 1, size_mode1)
+    rng = np.random.default_rng(5)
+    n = 33
+    d = np.arange(n, dtype=np.int64) * 16 + 730000
+    q_many = rng.integers(2, 4000, size=(5, n)).astype(np.uint16) & ~np.uint16(1)  # > 16 distinct QA words
+    s_many = rng.integers(-100, 10000, size=(7, 5, n)).astype(np.int16)
+    assert 2 * 5 * n % 16 != 0  # the raw QA part is padded
+    cut_last_section([synth.chip(cfg, 0, 0, 64), (d, s_many, q_many)], 0, size_mode0)
+
+
 @pytest.mark.parametrize('nt', ['1', '0'])
 def test_streaming_writer_fills_exactly_its_range(tmp_path, nt):
     """The encoder's streaming writer (ntw_*: band runs staged in L1, full lines out with

@@ -51,7 +51,7 @@ def main():
     out = sys.argv[1]
     os.makedirs(out, exist_ok=True)
     s = open(os.path.join(ROOT, 'lcmap-firebird_amd', 'csrc', 'ccd_encode.c')).read()
-    for a, b in (('#define ENC_HDR 128', 'static double T1, T2;\n#define ENC_HDR 128'),
+    for a, b in (('#include "ccd_enc_layout.h"', '#include "ccd_enc_layout.h"\nstatic double T1, T2;'),
                  ('    const int vec1 = have_vbmi2();', '    const int vec1 = have_vbmi2();\n    double T0 = omp_get_wtime();'),
                  ('        int bad = 0;  /* (pass 2',
                   '        T1 += omp_get_wtime() - T0; T0 = omp_get_wtime();\n        int bad = 0;  /* (pass 2'),
@@ -62,7 +62,8 @@ def main():
     open(os.path.join(out, 'enc_timed.c'), 'w').write(s)
     open(os.path.join(out, 'drv.c'), 'w').write(DRIVER)
     exe = os.path.join(out, 'encode_prof')
-    subprocess.run(['gcc', '-O3', '-fopenmp', '-I' + os.path.join(ROOT, 'include'), '-I' + out,
+    subprocess.run(['gcc', '-O3', '-fopenmp', '-I' + os.path.join(ROOT, 'include'),
+                    '-I' + os.path.join(ROOT, 'lcmap-firebird_amd', 'csrc'), '-I' + out,
                     os.path.join(out, 'drv.c'), '-o', exe], check=True)
     for blk in ('32', '1'):
         print('CCDGPU_ENCODE_BLOCK=%s' % blk, flush=True)
