@@ -407,6 +407,63 @@ int ccdgpu_classify(ccdgpu_ctx *ctx, const double *features, int64_t n_rows, flo
 int ccdgpu_classify_rows(ccdgpu_ctx *ctx, const double *aux, float *rfrawp, int64_t rows_cap, int64_t *n_rows,
                          double *kernel_seconds);
 
+/* Prediction of band values from segment models: the modelled surface reflectance of every pixel
+ * at dates of the caller's choosing (pyccd's ccd.models.lasso.predict over coefficient_matrix;
+ * annual composites, synthetic images, residuals of observations against their model).
+ *
+ * The rule.  A pixel's rows are ccdgpu_row records in table order; `dates` [n_dates] are proleptic
+ * ordinals shared by the pixels of the call, in any order, repeats allowed.
+ *   basis of a date t:   w = 2 pi / avg_days_yr;  w12 = w * (double)t;  w34 = 2.0 * w12;
+ *                        w56 = 3.0 * w12;  B = [t, cos w12, sin w12, cos w34, sin w34, cos w56,
+ *                        sin w56]   (the lines of the detection's own basis)
+ *   the row t takes:     rows with has_model == 0 (pyccd.default's row) are never taken;
+ *                        CCDGPU_COVER_SPAN    the first row in table order with sday <= t <= eday;
+ *                        CCDGPU_COVER_EXTEND  the row with the greatest sday <= t, ties going to the
+ *                                             later row (the model holds through the gap after a
+ *                                             break and after the last segment);
+ *                        no such row: the fill
+ *   value of band b:     v = intercept[b];  v = v + coef[b][k] * B[k] for k = 0 .. 6 in this order --
+ *                        double arithmetic on the row's float32 values widened, every product and
+ *                        every sum rounded on its own (no fused multiply-add)
+ *   CCDGPU_PREDICT_F32:  (float)v rounded to nearest; a NaN v and the fill are the quiet NaN
+ *                        0x7fc00000
+ *   CCDGPU_PREDICT_I16:  rint(v) (halves to even) clamped to [-32768, 32767]; a NaN v and the fill
+ *                        are -9999, the ARD fill value
+ * A restatement of these lines in numpy, given the same basis (ccdgpu_coefficient_matrix), is
+ * bit-equal; a value does not depend on how pixels or dates are batched or launched.
+ *   out        [7][n_pix][n_dates] float or int16: band-major, date-contiguous, dates in the order
+ *              given -- the layout of the `spectra` input, so a prediction at a chip's own dates
+ *              subtracts from its observations directly
+ *   seg_index  [n_pix][n_dates] int32, may be NULL: the taken row's index within its pixel, or -1 */
+enum { CCDGPU_COVER_SPAN = 0, CCDGPU_COVER_EXTEND = 1 };
+enum { CCDGPU_PREDICT_F32 = 0, CCDGPU_PREDICT_I16 = 1 };
+#define CCDGPU_PREDICT_MAX_DATE 3652059 /* date.max.toordinal() */
+/* The checks a prediction's arguments pass before anything reaches the device (no device needed).
+ * 0, or CCDGPU_EINVAL with the reason in ccdgpu_last_error(): a NULL array; a negative count;
+ * row_offsets[0] != 0, decreasing offsets, row_offsets[n_pix] != n_rows; a date outside
+ * 1 .. CCDGPU_PREDICT_MAX_DATE (or more than 2^31 - 1 dates); a non-finite or non-positive
+ * avg_days_yr; an unknown cover or dtype.  rows may be NULL when n_rows is 0, dates when n_dates is. */
+int ccdgpu_predict_check(int64_t n_pix, const int64_t *row_offsets, int64_t n_rows, const ccdgpu_row *rows,
+                         int64_t n_dates, const int64_t *dates, double avg_days_yr, int32_t cover, int32_t dtype);
+/* Host-table path: pixel p has rows[row_offsets[p] .. row_offsets[p + 1]).  Runs the check first
+ * (n_rows = row_offsets[n_pix]); synchronous; *kernel_seconds (may be NULL) gets the device time of
+ * the kernels.  n_pix == 0 or n_dates == 0 succeeds without a launch.  The output is produced on the
+ * device in slabs of whole pixels, so device memory stays bounded for any table.  Refused with
+ * CCDGPU_EINVAL while a detection begun with ccdgpu_run_slot_begin is not finished. */
+int ccdgpu_predict(ccdgpu_ctx *ctx, int64_t n_pix, const int64_t *row_offsets, const ccdgpu_row *rows, int64_t n_dates,
+                   const int64_t *dates, double avg_days_yr, int32_t cover, int32_t dtype, void *out, int32_t *seg_index,
+                   double *kernel_seconds);
+/* Chained path: the same for the pixels of chip `chip` of the context's last completed run, from
+ * its segments on the device -- each value narrowed to float32 exactly as the row packer does, so
+ * the output equals ccdgpu_predict's on the rows ccdgpu_fetch_rows gives for that chip.  A pixel
+ * without segments has no model.  Preconditions as ccdgpu_classify_rows (it works after
+ * ccdgpu_run_slot_end_rows too); a chip index out of range is CCDGPU_EINVAL. */
+int ccdgpu_predict_rows(ccdgpu_ctx *ctx, int32_t chip, int64_t n_dates, const int64_t *dates, double avg_days_yr,
+                        int32_t cover, int32_t dtype, void *out, int32_t *seg_index, double *kernel_seconds);
+/* The device's basis of `dates`: basis [n_dates][7], the B of the rule above -- the reference's
+ * coefficient_matrix(dates, avg_days_yr, 8) -- which is what makes exact tests of the rule possible. */
+int ccdgpu_coefficient_matrix(ccdgpu_ctx *ctx, int64_t n_dates, const int64_t *dates, double avg_days_yr, double *basis);
+
 /* Kernel statistics of the last run (per launch of the main detection kernel). */
 typedef struct ccdgpu_stats {
     double detect_ms;           /* average duration of the detection kernel (HIP events)   */

@@ -96,6 +96,17 @@ def _declare(L):
     L.ccdgpu_classify_rows.argtypes = [c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64, c.POINTER(c.c_int64),
                                        c.POINTER(c.c_double)]
     L.ccdgpu_classify_rows.restype = c.c_int
+    L.ccdgpu_predict_check.argtypes = [c.c_int64, c.c_void_p, c.c_int64, c.c_void_p, c.c_int64, c.c_void_p, c.c_double,
+                                       c.c_int32, c.c_int32]
+    L.ccdgpu_predict_check.restype = c.c_int
+    L.ccdgpu_predict.argtypes = [c.c_void_p, c.c_int64, c.c_void_p, c.c_void_p, c.c_int64, c.c_void_p, c.c_double,
+                                 c.c_int32, c.c_int32, c.c_void_p, c.c_void_p, c.POINTER(c.c_double)]
+    L.ccdgpu_predict.restype = c.c_int
+    L.ccdgpu_predict_rows.argtypes = [c.c_void_p, c.c_int32, c.c_int64, c.c_void_p, c.c_double, c.c_int32, c.c_int32,
+                                      c.c_void_p, c.c_void_p, c.POINTER(c.c_double)]
+    L.ccdgpu_predict_rows.restype = c.c_int
+    L.ccdgpu_coefficient_matrix.argtypes = [c.c_void_p, c.c_int64, c.c_void_p, c.c_double, c.c_void_p]
+    L.ccdgpu_coefficient_matrix.restype = c.c_int
     L.ccdgpu_detect_batch.argtypes = [c.c_void_p, c.POINTER(abi.Params), c.c_int32, c.c_int32,
                                       c.c_void_p, c.c_void_p, c.c_void_p, c.POINTER(abi.Result)]
     L.ccdgpu_result_free.argtypes = [c.POINTER(abi.Result)]
@@ -142,7 +153,8 @@ EXPORTS = ('ccdgpu_version', 'ccdgpu_last_error', 'ccdgpu_params_default', 'ccdg
            'ccdgpu_run_slot_begin', 'ccdgpu_run_query', 'ccdgpu_run_slot_end', 'ccdgpu_fetch_batch_rows_into',
            'ccdgpu_run_slot_begin_rows', 'ccdgpu_run_slot_end_rows', 'ccdgpu_encoded_check',
            'ccdgpu_forest_check', 'ccdgpu_forest_depth', 'ccdgpu_forest_set', 'ccdgpu_forest_clear',
-           'ccdgpu_classify', 'ccdgpu_classify_rows', 'ccdgpu_encoded_bound_flags', 'ccdgpu_encode_chips_flags')
+           'ccdgpu_classify', 'ccdgpu_classify_rows', 'ccdgpu_encoded_bound_flags', 'ccdgpu_encode_chips_flags',
+           'ccdgpu_predict_check', 'ccdgpu_predict', 'ccdgpu_predict_rows', 'ccdgpu_coefficient_matrix')
 
 
 def lib():
@@ -422,6 +434,63 @@ def _as_inputs(dates, spectra, qa):
     return dates, spectra, qa
 
 
+def _predict_dates(dates):
+    return np.ascontiguousarray(dates, dtype=np.int64).reshape(-1)
+
+
+def _predict_modes(cover, dtype):
+    """cover 'span' / 'extend' and dtype 'float32' / 'int16' (or numpy's) -> the library's codes;
+    integers pass through for the library to check."""
+    if not isinstance(cover, (int, np.integer)):
+        if cover not in abi.COVERS:
+            raise ValueError("cover must be 'span' or 'extend', not %r" % (cover,))
+        cover = abi.COVERS[cover]
+    if not isinstance(dtype, (int, np.integer)):
+        name = dtype if isinstance(dtype, str) else np.dtype(dtype).name
+        if name not in abi.PREDICT_DTYPES:
+            raise ValueError("dtype must be 'float32' or 'int16', not %r" % (dtype,))
+        dtype = abi.PREDICT_DTYPES[name]
+    return int(cover), int(dtype)
+
+
+def _predict_buffers(out, seg_index, n_pix, n_dates, dtype):
+    """(values, seg_index or None) to fill: the caller's arrays, checked, or new ones."""
+    want = np.dtype(np.int16 if dtype == abi.PREDICT_I16 else np.float32)
+    for a, shape, typ, name in ((out, (abi.NBANDS, n_pix, n_dates), want, 'out'),
+                                (seg_index, (n_pix, n_dates), np.dtype(np.int32), 'seg_index')):
+        if isinstance(a, np.ndarray) and (a.shape != shape or a.dtype != typ or not a.flags.c_contiguous or not a.flags.writeable):
+            raise ValueError('%s must be a writeable C-contiguous %s array of shape %r, got %s %r'
+                             % (name, typ.name, shape, a.dtype.name, a.shape))
+    if out is None:
+        out = np.empty((abi.NBANDS, n_pix, n_dates), dtype=want)
+    elif not isinstance(out, np.ndarray):
+        raise ValueError('out must be a numpy array or None')
+    if isinstance(seg_index, np.ndarray):
+        return out, seg_index
+    return out, (np.empty((n_pix, n_dates), dtype=np.int32) if seg_index else None)
+
+
+def predict_check(row_offsets, rows, dates, avg_days_yr=365.2425, cover=0, dtype=0, n_pix=None, n_rows=None):
+    """ccdgpu_predict_check (no device needed) over array-likes; None passes a NULL pointer, n_pix
+    / n_rows default to the arrays' sizes.  Raises ValueError with the library's message."""
+    off = None if row_offsets is None else np.ascontiguousarray(row_offsets, dtype=np.int64).reshape(-1)
+    r = None if rows is None else np.ascontiguousarray(rows, dtype=abi.ROW_DTYPE).reshape(-1)
+    d = None if dates is None else _predict_dates(dates)
+    if n_pix is None:
+        n_pix = 0 if off is None else off.shape[0] - 1
+    if n_rows is None:
+        n_rows = 0 if r is None else r.shape[0]
+    n_dates = 0 if d is None else d.shape[0]
+    if dates is None:
+        n_dates = 1  # (a NULL date vector of no dates is fine: ask for one)
+    if off is not None and off.shape[0] < n_pix + 1:
+        raise ValueError('row_offsets has %d entries, n_pix + 1 is %d' % (off.shape[0], n_pix + 1))
+    ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+    if lib().ccdgpu_predict_check(int(n_pix), ptr(off), int(n_rows), ptr(r), int(n_dates), ptr(d), float(avg_days_yr),
+                                  int(cover), int(dtype)) != 0:
+        raise ValueError(last_error())
+
+
 class Context(object):
     """One HIP device + stream (ccdgpu_ctx).  Not shared across threads."""
 
@@ -462,6 +531,8 @@ class Context(object):
         res = abi.Result()
         rc = lib().ccdgpu_detect_batch(self._ctx, ctypes.byref(p), n_pix, n_obs, dates.ctypes.data,
                                        spectra.ctypes.data, qa.ctypes.data, ctypes.byref(res))
+        if rc in (0, abi.E_QA):  # the context's last run is now this one-chip batch (predict_rows sizes its output by it)
+            self._keep, self._n_pix = (dates, spectra, qa), n_pix
         try:
             if rc not in (0, abi.E_QA):
                 _check(rc)
@@ -816,6 +887,65 @@ class Context(object):
         self.forest_seconds = secs.value
         self.forest_rows = nr.value
         return out[:nr.value]
+
+    # prediction of band values from segment models -----------------------------------------------
+    def coefficient_matrix(self, dates, avg_days_yr=365.2425):
+        """The device's basis of ``dates`` (ordinals): float64 [n_dates][7] = t, cos/sin of 1, 2
+        and 3 cycles per year -- the reference's coefficient_matrix(dates, avg_days_yr, 8)
+        (ccdgpu_coefficient_matrix)."""
+        d = _predict_dates(dates)
+        out = np.empty((d.shape[0], 7), dtype=np.float64)
+        _check(lib().ccdgpu_coefficient_matrix(self._ctx, d.shape[0], d.ctypes.data, float(avg_days_yr), out.ctypes.data))
+        return out
+
+    def predict(self, row_offsets, rows, dates, avg_days_yr=365.2425, cover='span', dtype='float32', seg_index=True,
+                out=None):
+        """Band values of a host table of segment rows at ``dates`` (ccdgpu_predict; the rule is in
+        include/ccdgpu.h): pixel p has rows[row_offsets[p]:row_offsets[p + 1]] (abi.ROW_DTYPE).
+        Returns (values [7][n_pix][n_dates] float32 or int16, seg_index int32 [n_pix][n_dates] or
+        None); the kernel seconds are in ``predict_seconds``.  ``out`` / ``seg_index`` may be arrays of
+        those shapes and types to fill instead of new ones -- the call is the copy of its output, and
+        page-locked arrays (``pinned_empty``), reused, receive it by DMA at the link's speed.
+        Arguments that fail ccdgpu_predict_check raise CcdGpuError (E_INVAL) with the library's message."""
+        off = np.ascontiguousarray(row_offsets, dtype=np.int64).reshape(-1)
+        r = np.ascontiguousarray(rows, dtype=abi.ROW_DTYPE).reshape(-1)
+        if off.shape[0] < 1:
+            raise ValueError('row_offsets must have n_pix + 1 entries')
+        d = _predict_dates(dates)
+        cover, dtype = _predict_modes(cover, dtype)
+        n_pix = off.shape[0] - 1
+        if int(off[-1]) != r.shape[0]:
+            raise ValueError('row_offsets end at %d, the table has %d rows' % (int(off[-1]), r.shape[0]))
+        out, idx = _predict_buffers(out, seg_index, n_pix, d.shape[0], dtype)
+        secs = ctypes.c_double(0.0)
+        _check(lib().ccdgpu_predict(self._ctx, n_pix, off.ctypes.data, r.ctypes.data, d.shape[0], d.ctypes.data,
+                                    float(avg_days_yr), cover, dtype, out.ctypes.data,
+                                    None if idx is None else idx.ctypes.data, ctypes.byref(secs)))
+        self.predict_seconds = secs.value
+        return out, idx
+
+    def predict_rows(self, chip, dates, avg_days_yr=365.2425, cover='span', dtype='float32', seg_index=True, out=None):
+        """``predict`` for the pixels of chip ``chip`` of the last completed run, from its segments
+        on the device (ccdgpu_predict_rows): the bytes ``predict`` gives on ``fetch_rows(chip, ..)``.
+        ``out`` / ``seg_index`` as for ``predict``."""
+        d = _predict_dates(dates)
+        cover, dtype = _predict_modes(cover, dtype)
+        batch = getattr(self, '_keep', None)
+        chip = int(chip)
+        if isinstance(batch, ChipBatch):
+            n_pix = int(batch.n_pix[chip]) if 0 <= chip < batch.n_chips else None
+        else:
+            n_pix = getattr(self, '_n_pix', None)
+        secs = ctypes.c_double(0.0)
+        if n_pix is None:  # nothing staged here, or no such chip: the library names the reason (no buffers passed)
+            _check(lib().ccdgpu_predict_rows(self._ctx, chip, d.shape[0], d.ctypes.data, float(avg_days_yr), cover, dtype,
+                                             None, None, ctypes.byref(secs)))
+            raise CcdGpuError(abi.E_INVAL, 'no completed run to predict from')
+        out, idx = _predict_buffers(out, seg_index, n_pix, d.shape[0], dtype)
+        _check(lib().ccdgpu_predict_rows(self._ctx, chip, d.shape[0], d.ctypes.data, float(avg_days_yr), cover, dtype,
+                                         out.ctypes.data, None if idx is None else idx.ctypes.data, ctypes.byref(secs)))
+        self.predict_seconds = secs.value
+        return out, idx
 
     def diag_counters(self):
         buf = (ctypes.c_uint64 * 48)()

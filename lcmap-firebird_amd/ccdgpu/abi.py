@@ -14,6 +14,13 @@ MAX_PEEK = 96
 FOREST_MAX_FEATURES = 64  # CCDGPU_FOREST_MAX_FEATURES
 FOREST_MAX_CLASSES = 32   # CCDGPU_FOREST_MAX_CLASSES
 ENC_PACK = 1              # CCDGPU_ENC_PACK: flag of ccdgpu_encode_chips_flags / ccdgpu_encoded_bound_flags
+COVER_SPAN, COVER_EXTEND = 0, 1  # CCDGPU_COVER_*: which row a date takes (include/ccdgpu.h)
+PREDICT_F32, PREDICT_I16 = 0, 1  # CCDGPU_PREDICT_*: output type of a prediction
+PREDICT_MAX_DATE = 3652059       # CCDGPU_PREDICT_MAX_DATE: date.max.toordinal()
+PREDICT_FILL_I16 = -9999         # the int16 fill (ARD's); the float32 fill is NaN
+PREDICT_CACHE_ROWS = 16          # CCD_PREDICT_CACHE_ROWS (csrc/ccd_predict.h): models a block keeps in LDS at a time
+COVERS = {'span': COVER_SPAN, 'extend': COVER_EXTEND}
+PREDICT_DTYPES = {'float32': PREDICT_F32, 'int16': PREDICT_I16}
 BANDS = ('blue', 'green', 'red', 'nir', 'swir1', 'swir2', 'thermal')
 PROCEDURES = ('standard_procedure', 'permanent_snow_procedure', 'insufficient_clear_procedure')
 

@@ -25,6 +25,7 @@
 #include "../../include/ccdgpu.h"
 #include "ccd_device.h"
 #include "ccd_enc_layout.h"
+#include "ccd_predict.h"
 
 namespace {
 
@@ -277,6 +278,16 @@ struct ccdgpu_ctx {
     DevBuf<double> f_x, f_aux;
     DevBuf<float> f_out;
     hipEvent_t f_ev[2] = {nullptr, nullptr};
+    // prediction of band values (ccd_predict.hip): pixels whose output the device holds at a time
+    // (CCDGPU_PREDICT_SLAB_PIXELS, test knob; 0: as many as keep a slab within PREDICT_SLAB_BYTES)
+    // and the scratch of a slab -- dates, basis, offsets, table rows, values, row indices
+    int64_t predict_slab_pixels = 0;
+    DevBuf<int64_t> p_dates, p_off;
+    DevBuf<double> p_basis;
+    DevBuf<ccdgpu_row> p_rows;
+    DevBuf<unsigned char> p_out;
+    DevBuf<int32_t> p_idx;
+    hipEvent_t p_ev[2] = {nullptr, nullptr};
     ~ccdgpu_ctx() {
         for (auto *b : {&dates, &sdates, &offsets, &chip_obs_off, &chip_pix_off, &chip_data_off, &row_off, &seg_off1, &b64_off})
             b->release();
@@ -323,6 +334,14 @@ struct ccdgpu_ctx {
         f_aux.release();
         f_out.release();
         for (auto &e : f_ev)
+            if (e) (void)hipEventDestroy(e);
+        p_dates.release();
+        p_off.release();
+        p_basis.release();
+        p_rows.release();
+        p_out.release();
+        p_idx.release();
+        for (auto &e : p_ev)
             if (e) (void)hipEventDestroy(e);
         if (stream) (void)hipStreamDestroy(stream);
         release_arg_slot(arg_slot);
@@ -528,6 +547,7 @@ int ccdgpu_init_copy_cus(int device, int copy_cus, ccdgpu_ctx **out) {
     if (const char *v = std::getenv("CCDGPU_ROWS_FUSED")) c->rows_fused = std::atoi(v) != 0;
     if (const char *v = std::getenv("CCDGPU_KEEP_SLOTS")) c->keep_slots = std::atoi(v) != 0;
     if (const char *v = std::getenv("CCDGPU_POOL_PER_PIXEL")) c->pool_per_pixel = std::max(1, std::atoi(v));
+    if (const char *v = std::getenv("CCDGPU_PREDICT_SLAB_PIXELS")) c->predict_slab_pixels = std::max(0, std::atoi(v));
     *out = c;
     return 0;
 }
@@ -1838,6 +1858,176 @@ int ccdgpu_classify_rows(ccdgpu_ctx *c, const double *aux, float *rfrawp, int64_
     float ms = 0.f;
     (void)hipEventElapsedTime(&ms, c->f_ev[0], c->f_ev[1]);
     if (kernel_seconds) *kernel_seconds = ms * 1e-3;
+    return 0;
+}
+
+// ---- prediction of band values from segment models (include/ccdgpu.h; kernels in ccd_predict.hip)
+
+// device bytes of a slab's output when the context names no pixel count
+static const int64_t PREDICT_SLAB_BYTES = (int64_t)256 << 20;
+
+static int predict_check_dates(int64_t n_dates, const int64_t *dates, double avg_days_yr) {
+    if (n_dates < 0) return fail(CCDGPU_EINVAL, "predict: n_dates must be >= 0, got " + std::to_string(n_dates));
+    if (n_dates > INT32_MAX) return fail(CCDGPU_EINVAL, "predict: n_dates must be < 2^31, got " + std::to_string(n_dates));
+    if (n_dates > 0 && !dates) return fail(CCDGPU_EINVAL, "predict: dates is NULL");
+    if (!std::isfinite(avg_days_yr) || !(avg_days_yr > 0.0))
+        return fail(CCDGPU_EINVAL, "predict: avg_days_yr must be finite and > 0, got " + std::to_string(avg_days_yr));
+    for (int64_t i = 0; i < n_dates; ++i)
+        if (dates[i] < 1 || dates[i] > CCDGPU_PREDICT_MAX_DATE)
+            return fail(CCDGPU_EINVAL, "predict: dates[" + std::to_string(i) + "] = " + std::to_string(dates[i]) +
+                                           " is outside 1 .. " + std::to_string(CCDGPU_PREDICT_MAX_DATE));
+    return 0;
+}
+
+static int predict_check_modes(int32_t cover, int32_t dtype) {
+    if (cover != CCDGPU_COVER_SPAN && cover != CCDGPU_COVER_EXTEND)
+        return fail(CCDGPU_EINVAL, "predict: unknown cover " + std::to_string(cover));
+    if (dtype != CCDGPU_PREDICT_F32 && dtype != CCDGPU_PREDICT_I16)
+        return fail(CCDGPU_EINVAL, "predict: unknown dtype " + std::to_string(dtype));
+    return 0;
+}
+
+int ccdgpu_predict_check(int64_t n_pix, const int64_t *row_offsets, int64_t n_rows, const ccdgpu_row *rows, int64_t n_dates,
+                         const int64_t *dates, double avg_days_yr, int32_t cover, int32_t dtype) {
+    if (n_pix < 0) return fail(CCDGPU_EINVAL, "predict: n_pix must be >= 0, got " + std::to_string(n_pix));
+    if (n_rows < 0) return fail(CCDGPU_EINVAL, "predict: n_rows must be >= 0, got " + std::to_string(n_rows));
+    if (!row_offsets) return fail(CCDGPU_EINVAL, "predict: row_offsets is NULL");
+    if (n_rows > 0 && !rows) return fail(CCDGPU_EINVAL, "predict: rows is NULL");
+    if (row_offsets[0] != 0)
+        return fail(CCDGPU_EINVAL, "predict: row_offsets[0] must be 0, got " + std::to_string(row_offsets[0]));
+    for (int64_t p = 0; p < n_pix; ++p)
+        if (row_offsets[p + 1] < row_offsets[p])
+            return fail(CCDGPU_EINVAL, "predict: row_offsets decrease at pixel " + std::to_string(p) + " (" +
+                                           std::to_string(row_offsets[p]) + " -> " + std::to_string(row_offsets[p + 1]) + ")");
+    if (row_offsets[n_pix] != n_rows)
+        return fail(CCDGPU_EINVAL, "predict: row_offsets[n_pix] is " + std::to_string(row_offsets[n_pix]) + ", n_rows is " +
+                                       std::to_string(n_rows));
+    int rc = predict_check_dates(n_dates, dates, avg_days_yr);
+    if (rc) return rc;
+    return predict_check_modes(cover, dtype);
+}
+
+static int predict_events(ccdgpu_ctx *c) {
+    for (auto &e : c->p_ev)
+        if (!e) HIPCHK(hipEventCreate(&e));
+    return 0;
+}
+
+// Both paths, slab by slab over whole pixels: pixel p has the models h_off[p] .. h_off[p + 1] of the
+// host table h_rows (uploaded per slab) or, with h_rows NULL, of the device segments d_seg [n_seg].
+// A slab's values come back as 7 copies, one per band, into the caller's [7][n_pix][n_dates].
+static int predict_run(ccdgpu_ctx *c, const ccdgpu_row *h_rows, const ccdgpu_segment *d_seg, int64_t n_seg,
+                       const int64_t *h_off, int64_t n_pix, int64_t n_dates, const int64_t *dates, double avg_days_yr,
+                       int32_t cover, int32_t dtype, void *out, int32_t *seg_index, double *kernel_seconds) {
+    HIPCHK(hipSetDevice(c->device));
+    int rc = predict_events(c);
+    if (rc) return rc;
+    const int64_t esz = dtype == CCDGPU_PREDICT_I16 ? 2 : 4;
+    int64_t slab = c->predict_slab_pixels > 0 ? c->predict_slab_pixels
+                                              : std::max<int64_t>(1, PREDICT_SLAB_BYTES / (n_dates * (CCDGPU_NBANDS * esz + 4)));
+    slab = std::min(slab, std::min(n_pix, ccdk_predict_max_pixels()));
+    if ((rc = c->p_dates.ensure((size_t)n_dates)) || (rc = c->p_basis.ensure((size_t)n_dates * 8)) ||
+        (rc = c->p_off.ensure((size_t)slab + 1)) || (rc = c->p_out.ensure((size_t)(CCDGPU_NBANDS * slab * n_dates * esz))) ||
+        (seg_index && (rc = c->p_idx.ensure((size_t)(slab * n_dates)))))
+        return rc;
+    hipStream_t ax = c->aux;
+    HIPCHK(hipMemcpyAsync(c->p_dates.p, dates, sizeof(int64_t) * (size_t)n_dates, hipMemcpyHostToDevice, ax));
+    double secs = 0.0;
+    for (int64_t p0 = 0; p0 < n_pix; p0 += slab) {
+        const int64_t np = std::min(slab, n_pix - p0);
+        const int64_t r0 = h_off[p0], nr = h_off[p0 + np] - r0;
+        HIPCHK(hipMemcpyAsync(c->p_off.p, h_off + p0, sizeof(int64_t) * (size_t)(np + 1), hipMemcpyHostToDevice, ax));
+        if (h_rows && nr > 0) {
+            if ((rc = c->p_rows.ensure((size_t)nr))) {
+                (void)hipStreamSynchronize(ax);
+                return rc;
+            }
+            HIPCHK(hipMemcpyAsync(c->p_rows.p, h_rows + r0, sizeof(ccdgpu_row) * (size_t)nr, hipMemcpyHostToDevice, ax));
+        }
+        HIPCHK(hipEventRecord(c->p_ev[0], ax));
+        int bad = p0 == 0 ? ccdk_predict_basis(c->p_dates.p, n_dates, avg_days_yr, c->p_basis.p, ax) : 0;
+        int32_t *idx = seg_index ? c->p_idx.p : nullptr;
+        if (!bad)
+            bad = h_rows ? ccdk_predict_rows(c->p_rows.p, c->p_off.p, r0, nr, np, c->p_dates.p, c->p_basis.p, n_dates, cover, dtype,
+                                             c->p_out.p, idx, ax)
+                         : ccdk_predict_segments(d_seg, c->p_off.p, 0, n_seg, np, c->p_dates.p, c->p_basis.p, n_dates, cover,
+                                                 dtype, c->p_out.p, idx, ax);
+        if (bad) {
+            (void)hipStreamSynchronize(ax);
+            return fail(CCDGPU_EHIP, "predict kernel launch failed");
+        }
+        HIPCHK(hipEventRecord(c->p_ev[1], ax));
+        const size_t band = (size_t)(np * n_dates * esz);
+        for (int b = 0; b < CCDGPU_NBANDS; ++b)
+            HIPCHK(hipMemcpyAsync(static_cast<unsigned char *>(out) + ((size_t)b * n_pix + p0) * n_dates * esz,
+                                  c->p_out.p + (size_t)b * band, band, hipMemcpyDeviceToHost, ax));
+        if (seg_index)
+            HIPCHK(hipMemcpyAsync(seg_index + p0 * n_dates, c->p_idx.p, sizeof(int32_t) * (size_t)(np * n_dates),
+                                  hipMemcpyDeviceToHost, ax));
+        HIPCHK(hipStreamSynchronize(ax));
+        float ms = 0.f;
+        (void)hipEventElapsedTime(&ms, c->p_ev[0], c->p_ev[1]);
+        secs += ms * 1e-3;
+    }
+    if (kernel_seconds) *kernel_seconds = secs;
+    return 0;
+}
+
+int ccdgpu_predict(ccdgpu_ctx *c, int64_t n_pix, const int64_t *row_offsets, const ccdgpu_row *rows, int64_t n_dates,
+                   const int64_t *dates, double avg_days_yr, int32_t cover, int32_t dtype, void *out, int32_t *seg_index,
+                   double *kernel_seconds) {
+    if (kernel_seconds) *kernel_seconds = 0.0;
+    if (!c) return fail(CCDGPU_EINVAL, "NULL ctx");
+    if (c->pending) return fail(CCDGPU_EINVAL, "a detection begun with ccdgpu_run_slot_begin is not finished");
+    if (n_pix < 0) return fail(CCDGPU_EINVAL, "predict: n_pix must be >= 0, got " + std::to_string(n_pix));
+    if (!row_offsets) return fail(CCDGPU_EINVAL, "predict: row_offsets is NULL");
+    int rc = ccdgpu_predict_check(n_pix, row_offsets, row_offsets[n_pix], rows, n_dates, dates, avg_days_yr, cover, dtype);
+    if (rc) return rc;
+    if (n_pix == 0 || n_dates == 0) return 0;
+    if (!out) return fail(CCDGPU_EINVAL, "predict: out is NULL");
+    return predict_run(c, rows, nullptr, 0, row_offsets, n_pix, n_dates, dates, avg_days_yr, cover, dtype, out, seg_index,
+                       kernel_seconds);
+}
+
+int ccdgpu_predict_rows(ccdgpu_ctx *c, int32_t chip, int64_t n_dates, const int64_t *dates, double avg_days_yr, int32_t cover,
+                        int32_t dtype, void *out, int32_t *seg_index, double *kernel_seconds) {
+    if (kernel_seconds) *kernel_seconds = 0.0;
+    if (!c) return fail(CCDGPU_EINVAL, "NULL ctx");
+    if (c->pending) return fail(CCDGPU_EINVAL, "a detection begun with ccdgpu_run_slot_begin is not finished");
+    if (!c->ran || c->shape.n_chips() <= 0) return fail(CCDGPU_EINVAL, "no completed run to predict from");
+    const int64_t total = c->shape.total_pix();
+    if ((int64_t)c->h_offsets.size() < total + 1) return fail(CCDGPU_EINVAL, "no completed run to predict from");
+    if (chip < 0 || chip >= c->shape.n_chips())
+        return fail(CCDGPU_EINVAL, "predict_rows: chip " + std::to_string(chip) + " is outside [0, " +
+                                       std::to_string(c->shape.n_chips()) + ")");
+    int rc = predict_check_dates(n_dates, dates, avg_days_yr);
+    if (rc || (rc = predict_check_modes(cover, dtype))) return rc;
+    if (n_dates == 0) return 0;
+    if (!out) return fail(CCDGPU_EINVAL, "predict: out is NULL");
+    const int64_t p0 = c->shape.pix_off[chip];
+    return predict_run(c, nullptr, c->csr.p, c->h_offsets[total], c->h_offsets.data() + p0, c->shape.npix[chip], n_dates, dates,
+                       avg_days_yr, cover, dtype, out, seg_index, kernel_seconds);
+}
+
+int ccdgpu_coefficient_matrix(ccdgpu_ctx *c, int64_t n_dates, const int64_t *dates, double avg_days_yr, double *basis) {
+    if (!c) return fail(CCDGPU_EINVAL, "NULL ctx");
+    if (c->pending) return fail(CCDGPU_EINVAL, "a detection begun with ccdgpu_run_slot_begin is not finished");
+    int rc = predict_check_dates(n_dates, dates, avg_days_yr);
+    if (rc) return rc;
+    if (n_dates == 0) return 0;
+    if (!basis) return fail(CCDGPU_EINVAL, "predict: basis is NULL");
+    HIPCHK(hipSetDevice(c->device));
+    if ((rc = c->p_dates.ensure((size_t)n_dates)) || (rc = c->p_basis.ensure((size_t)n_dates * 8))) return rc;
+    hipStream_t ax = c->aux;
+    HIPCHK(hipMemcpyAsync(c->p_dates.p, dates, sizeof(int64_t) * (size_t)n_dates, hipMemcpyHostToDevice, ax));
+    if (ccdk_predict_basis(c->p_dates.p, n_dates, avg_days_yr, c->p_basis.p, ax)) {
+        (void)hipStreamSynchronize(ax);
+        return fail(CCDGPU_EHIP, "predict kernel launch failed");
+    }
+    std::vector<double> b8((size_t)n_dates * 8);
+    HIPCHK(hipMemcpyAsync(b8.data(), c->p_basis.p, sizeof(double) * b8.size(), hipMemcpyDeviceToHost, ax));
+    HIPCHK(hipStreamSynchronize(ax));
+    for (int64_t i = 0; i < n_dates; ++i) std::memcpy(basis + i * 7, b8.data() + i * 8, sizeof(double) * 7);
     return 0;
 }
 
