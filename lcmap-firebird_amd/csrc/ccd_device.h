@@ -106,13 +106,10 @@ int ccdk_pack_rows(const ccdgpu_segment *seg, const int64_t *seg_off, const int6
                    int32_t mask_words, int32_t n_pix, int32_t n_obs, int32_t cx, int32_t cy, int32_t width,
                    ccdgpu_row *rows, int8_t *mask, const unsigned long long *skip, int64_t seg_cap, int64_t rows_cap,
                    void *stream);
-// the batch chain of ccdgpu_run_slot_begin_rows (ccd_rows.hip): pool -> CSR with the segment
-// count read on the device (counters[1], at most cap); rows per pixel for the row-offset scan
-// (overflow: the detection's pool-overflow flag -- set, the chain's kernels write nothing and the
-// host reruns the batch with a larger pool)
-int ccdk_scatter_dev(const ccdgpu_segment *pool, const int32_t *pool_seq, const unsigned long long *n_pool_dev,
-                     const unsigned long long *overflow, int64_t cap, const int64_t *offsets,
-                     const int64_t *chip_pix_off, int32_t n_chips, ccdgpu_segment *out, void *stream);
+// the batch chain of ccdgpu_run_slot_begin_rows (ccd_rows.hip): rows per pixel for the row-offset
+// scan, then pool -> CSR and rows with the segment count read on the device (counters[1], at most
+// cap) (overflow: the detection's pool-overflow flag -- set, the chain's kernels write nothing and
+// the host reruns the batch with a larger pool)
 int ccdk_row_counts(const int32_t *nseg, int64_t *offsets, int64_t n_pix, int64_t *rc, void *stream);
 // pool -> CSR (and, rows != nullptr, the float32 rows) in one pass; segment count from n_pool_dev
 // when given, else n_pool_host; writes nothing when *overflow (ccd_rows.hip)
@@ -124,10 +121,6 @@ int ccdk_pool_rows(const ccdgpu_segment *pool, const int32_t *pool_seq, const un
 int ccdk_default_rows(const int32_t *nseg, int64_t n_pix, const unsigned long long *overflow,
                       const int64_t *chip_pix_off, int32_t n_chips, const int64_t *row_off, const int32_t *chip_xy,
                       int32_t width, ccdgpu_row *rows, int64_t rows_cap, void *stream);
-// pool -> CSR; the segment's pixel field becomes the pixel index within its chip
-int ccdk_scatter(const ccdgpu_segment *pool, const int32_t *pool_seq, int64_t n_pool,
-                 const int64_t *offsets, const int64_t *chip_pix_off, int32_t n_chips, ccdgpu_segment *out,
-                 void *stream);
 // random-forest inference (ccd_forest.hip).  Device forest: one relocatable blob per tree, blobs
 // back to back in `pool` -- CcdForestNode[n_t] in breadth-first order (root at 0, the two
 // children of a node adjacent: right = left + 1), then the leaves' class vectors; indices inside

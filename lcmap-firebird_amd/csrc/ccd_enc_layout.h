@@ -1,5 +1,5 @@
 /* ccd_enc_layout.h -- the byte layout of a transport-encoded batch, defined once for the host
- * encoder (ccd_encode.c), the host check (encoded_check in ccdgpu_api.cpp) and the device readers
+ * encoder (ccd_encode.c), the host check (encoded_check in ccdgpu_checks.cpp) and the device readers
  * (ccd_decode_enc / ccd_decode_pack in ccd_pack.hip, px_setup in ccd_kernels.hip).
  *
  * The normative description is the comment above ccdgpu_encode_chips in include/ccdgpu.h; the

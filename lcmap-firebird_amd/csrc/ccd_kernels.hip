@@ -15,7 +15,6 @@
 //                   lookforward with closest-DOY comparison RMSE, catch (change.py), 4/6/8-coef
 //                   Lasso (models/lasso.py = sklearn 0.18 coordinate descent, here in Gram form),
 //                   permanent-snow / insufficient-clear single fits (procedures.py).
-//   ccdk_scatter -- segment pool -> CSR by pixel.
 //
 // Parallel mapping inside a wave (all control flow is wave-uniform; every reduction is a
 // shuffle butterfly whose result is bit-identical in all lanes):
@@ -4135,28 +4134,6 @@ __global__ __launch_bounds__(256) void ccd_prep(const int64_t *dates, const int3
     }
 }
 
-// Pool -> CSR: one wave per pooled segment, dwords copied lane-parallel.
-__global__ __launch_bounds__(256) void ccd_scatter(const ccdgpu_segment *pool, const int32_t *seq, int64_t n_pool,
-                                                   const int64_t *offsets, const int64_t *chip_pix_off,
-                                                   int n_chips, ccdgpu_segment *out) {
-    const int64_t s = (int64_t)blockIdx.x * (blockDim.x / W) + threadIdx.x / W;
-    if (s >= n_pool) return;
-    const int l = threadIdx.x % W;
-    const int gp = pool[s].pixel;
-    int lo = 0, hi = n_chips - 1;  // chip of the pixel
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (chip_pix_off[mid] <= gp) lo = mid;
-        else hi = mid - 1;
-    }
-    const int64_t dst = offsets[gp] + seq[s];
-    const uint32_t *src = reinterpret_cast<const uint32_t *>(pool + s);
-    uint32_t *dd = reinterpret_cast<uint32_t *>(out + dst);
-    constexpr int NW = (int)(sizeof(ccdgpu_segment) / 4);
-    constexpr int PIXW = (int)(offsetof(ccdgpu_segment, pixel) / 4);
-    for (int i = l; i < NW; i += W) dd[i] = (i == PIXW) ? (uint32_t)(gp - chip_pix_off[lo]) : src[i];
-}
-
 }  // namespace
 
 extern "C" int ccdk_prep(const int64_t *dates, int32_t n_chips, const int32_t *chip_nobs, const int64_t *chip_obs_off,
@@ -4206,16 +4183,5 @@ extern "C" int ccdk_detect(int32_t grid, int variant, int32_t n_obs, int arg_slo
     case 4: hipLaunchKernelGGL(ccd_detect_w4, dim3(grid), dim3(64), lds, (hipStream_t)stream, arg_slot); break;
     default: hipLaunchKernelGGL(ccd_detect_w3, dim3(grid), dim3(64), lds, (hipStream_t)stream, arg_slot); break;
     }
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-extern "C" int ccdk_scatter(const ccdgpu_segment *pool, const int32_t *pool_seq, int64_t n_pool,
-                            const int64_t *offsets, const int64_t *chip_pix_off, int32_t n_chips,
-                            ccdgpu_segment *out, void *stream) {
-    if (n_pool <= 0) return 0;
-    const int per_block = 256 / W;
-    const int64_t blocks = (n_pool + per_block - 1) / per_block;
-    hipLaunchKernelGGL(ccd_scatter, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, pool,
-                       pool_seq, n_pool, offsets, chip_pix_off, n_chips, out);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }

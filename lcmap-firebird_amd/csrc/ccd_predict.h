@@ -1,5 +1,5 @@
 // ccd_predict.h -- launchers of ccd_predict.hip (prediction of band values from segment models),
-// called by ccdgpu_api.cpp.  All pointers are device pointers; a launcher returns 0, or -1 when the
+// called by ccdgpu_predict.cpp.  All pointers are device pointers; a launcher returns 0, or -1 when the
 // launch was refused.
 #ifndef CCD_PREDICT_H
 #define CCD_PREDICT_H

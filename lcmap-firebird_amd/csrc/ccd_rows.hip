@@ -79,44 +79,15 @@ __global__ __launch_bounds__(256) void ccd_pack_rows(const ccdgpu_segment *__res
     }
 }
 
-// Pool -> CSR with the segment count read on the device (counters[1] of the detection, for the
-// batch chain that is enqueued before the count is known): grid-stride over the pooled segments,
-// one wave per segment, its dwords copied lane-parallel; the pixel field becomes the pixel index
-// within its chip (the same result as ccd_scatter in ccd_kernels.hip).
-__global__ __launch_bounds__(256) void ccd_scatter_dev(const ccdgpu_segment *__restrict__ pool, const int32_t *__restrict__ seq,
-                                                       const unsigned long long *__restrict__ n_pool_dev,
-                                                       const unsigned long long *__restrict__ overflow, int64_t cap,
-                                                       const int64_t *__restrict__ offsets, const int64_t *__restrict__ chip_pix_off,
-                                                       int n_chips, ccdgpu_segment *__restrict__ out) {
-    if (overflow && *overflow) return;  // the pool overflowed: the host reruns the batch
-    const int64_t n = (int64_t)(*n_pool_dev < (unsigned long long)cap ? *n_pool_dev : (unsigned long long)cap);
-    const int l = threadIdx.x % W;
-    const int64_t nw = (int64_t)gridDim.x * (blockDim.x / W);
-    for (int64_t s = (int64_t)blockIdx.x * (blockDim.x / W) + threadIdx.x / W; s < n; s += nw) {
-        const int gp = pool[s].pixel;
-        int lo = 0, hi = n_chips - 1;  // chip of the pixel
-        while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if (chip_pix_off[mid] <= gp) lo = mid;
-            else hi = mid - 1;
-        }
-        const int64_t dst = offsets[gp] + seq[s];
-        if (dst < 0 || dst >= cap) continue;
-        const uint32_t *src = reinterpret_cast<const uint32_t *>(pool + s);
-        uint32_t *dd = reinterpret_cast<uint32_t *>(out + dst);
-        constexpr int NW = (int)(sizeof(ccdgpu_segment) / 4);
-        constexpr int PIXW = (int)(offsetof(ccdgpu_segment, pixel) / 4);
-        for (int i = l; i < NW; i += W) dd[i] = (i == PIXW) ? (uint32_t)(gp - chip_pix_off[lo]) : src[i];
-    }
-}
-
 // Pool -> CSR and rows in one pass (batch chain): each wave takes 64 pooled segments, every lane
 // resolves one of them (pixel, chip, position in the CSR and in the rows: the dependent loads
 // of 64 segments in flight at once), then the wave copies them one after the other, all lanes
 // over one segment's dwords -- the CSR record (the pixel field becoming the pixel index within
 // its chip) and, with rows != nullptr, its float32 row (lanes over the row's 78 dwords, each
-// converting its double; the same values as ccd_pack_rows).  n_pool_dev / overflow as
-// ccd_scatter_dev; chip_xy [2 n_chips] the chips' (cx, cy).
+// converting its double; the same values as ccd_pack_rows).  n_pool_dev: the segment count read
+// on the device (counters[1] of the detection, for the batch chain that is enqueued before the
+// count is known), at most cap; overflow: the pool overflowed, the host reruns the batch;
+// chip_xy [2 n_chips] the chips' (cx, cy).
 constexpr int SEG_DW = (int)(sizeof(ccdgpu_segment) / 4);
 constexpr int ROW_DW = (int)(sizeof(ccdgpu_row) / 4);
 static_assert(ROW_DW == 8 + 10 * CCDGPU_NBANDS, "ccdgpu_row layout");
@@ -241,14 +212,6 @@ __global__ __launch_bounds__(256) void ccd_row_counts(const int32_t *__restrict_
 }
 
 }  // namespace
-
-extern "C" int ccdk_scatter_dev(const ccdgpu_segment *pool, const int32_t *pool_seq, const unsigned long long *n_pool_dev,
-                                const unsigned long long *overflow, int64_t cap, const int64_t *offsets,
-                                const int64_t *chip_pix_off, int32_t n_chips, ccdgpu_segment *out, void *stream) {
-    hipLaunchKernelGGL(ccd_scatter_dev, dim3(256), dim3(256), 0, (hipStream_t)stream, pool, pool_seq, n_pool_dev, overflow,
-                       cap, offsets, chip_pix_off, n_chips, out);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
 
 extern "C" int ccdk_row_counts(const int32_t *nseg, int64_t *offsets, int64_t n_pix, int64_t *rc, void *stream) {
     const int64_t blocks = (n_pix + 1 + 255) / 256;

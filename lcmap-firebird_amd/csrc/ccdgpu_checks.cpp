@@ -1,0 +1,401 @@
+// ccdgpu_checks.cpp -- the part of the host API that touches no device: the error state, the
+// default parameters and the validators of parameters, shapes, transport-encoded batches, forests
+// and prediction requests.  The device code trusts what passes here, so this unit is kept free of
+// HIP and builds with a plain C++ compiler too (tests/native/host_checks.cpp runs it under
+// sanitizers).
+#include "ccdgpu_checks.h"
+
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <cstring>
+
+#include "ccd_enc_layout.h"
+
+namespace ccdhost {
+
+namespace {
+
+thread_local std::string g_err;
+
+double chi2_5_cdf(double x) {
+    if (x <= 0) return 0.0;
+    return std::erf(std::sqrt(x / 2.0)) - std::sqrt(2.0 * x / M_PI) * std::exp(-x / 2.0) * (1.0 + x / 3.0);
+}
+
+// inverse chi-square(5) cdf (change.adjustchgthresh uses scipy chi2.ppf(pt_cg, 5))
+double chi2_5_ppf(double p) {
+    double lo = 0.0, hi = 400.0;
+    for (int i = 0; i < 200; ++i) {
+        const double mid = 0.5 * (lo + hi);
+        if (chi2_5_cdf(mid) < p) lo = mid;
+        else hi = mid;
+    }
+    return 0.5 * (lo + hi);
+}
+
+// "encoded batch: chip N" + what is wrong with it
+int enc_fail(int32_t chip, const std::string &what) {
+    return fail(CCDGPU_EINVAL, "encoded batch: chip " + std::to_string(chip) + what);
+}
+
+// the kept-offset table of a mode 1 or 2 section: a run of at most n_obs per pixel, ending at kept
+int enc_check_koff(int32_t chip, const uint32_t *koff, int64_t n_pix, int64_t n_obs, int64_t kept) {
+    if (koff[0] != 0 || (int64_t)koff[n_pix] != kept) return enc_fail(chip, " kept-offset table does not end at kept");
+    for (int64_t q = 0; q < n_pix; ++q)
+        if (koff[q + 1] < koff[q] || (int64_t)(koff[q + 1] - koff[q]) > n_obs)
+            return enc_fail(chip, " kept-offset table is not a run per pixel");
+    return 0;
+}
+
+}  // namespace
+
+int fail(int code, const std::string &msg) {
+    g_err = msg;
+    return code;
+}
+
+int make_shape(int32_t n_chips, const int32_t *n_pix, const int32_t *n_obs, Shape &s) {
+    if (n_chips <= 0) return fail(CCDGPU_EINVAL, "n_chips must be > 0");
+    if (!n_pix || !n_obs) return fail(CCDGPU_EINVAL, "NULL n_pix / n_obs array");
+    s.npix.assign(n_pix, n_pix + n_chips);
+    s.nobs.assign(n_obs, n_obs + n_chips);
+    s.obs_off.assign(n_chips + 1, 0);
+    s.pix_off.assign(n_chips + 1, 0);
+    s.data_off.assign(n_chips + 1, 0);
+    s.n_obs_max = 0;
+    for (int c = 0; c < n_chips; ++c) {
+        if (n_pix[c] <= 0) return fail(CCDGPU_EINVAL, "chip " + std::to_string(c) + ": n_pix must be > 0");
+        if (n_obs[c] <= 0 || n_obs[c] > CCDGPU_MAX_OBS)
+            return fail(CCDGPU_EINVAL, "chip " + std::to_string(c) + ": n_obs must be in [1, " + std::to_string(CCDGPU_MAX_OBS) + "]");
+        s.obs_off[c + 1] = s.obs_off[c] + n_obs[c];
+        s.pix_off[c + 1] = s.pix_off[c] + n_pix[c];
+        s.data_off[c + 1] = s.data_off[c] + (int64_t)n_pix[c] * n_obs[c];
+        s.n_obs_max = std::max(s.n_obs_max, n_obs[c]);
+    }
+    if (s.total_pix() >= (int64_t)1 << 31) return fail(CCDGPU_EINVAL, "more than 2^31 - 1 pixels in one batch");
+    return 0;
+}
+
+int check_params(const ccdgpu_params *p) {
+    if (!p) return fail(CCDGPU_EINVAL, "params is NULL");
+    if (p->peek_size < 1 || p->peek_size > CCDGPU_MAX_PEEK)
+        return fail(CCDGPU_EINVAL, "peek_size must be in [1, " + std::to_string(CCDGPU_MAX_PEEK) + "]");
+    if (p->meow_size < 5) return fail(CCDGPU_EINVAL, "meow_size must be >= 5 (Tmask needs > 4 observations)");
+    if (p->coef_min != 4 && p->coef_min != 6 && p->coef_min != 8)
+        return fail(CCDGPU_EINVAL, "coefficient counts must be 4, 6 or 8");
+    if ((p->coef_mid != 4 && p->coef_mid != 6 && p->coef_mid != 8) || (p->coef_max != 4 && p->coef_max != 6 && p->coef_max != 8))
+        return fail(CCDGPU_EINVAL, "coefficient counts must be 4, 6 or 8");
+    if (p->lasso_max_iter < 1) return fail(CCDGPU_EINVAL, "lasso_max_iter must be >= 1");
+    if ((p->detection_bands & ~0x7Fu) || (p->tmask_bands & ~0x7Fu))
+        return fail(CCDGPU_EINVAL, "band masks must only use bits 0..6");
+    if (p->argsort_stable != 0 && p->argsort_stable != 1) return fail(CCDGPU_EINVAL, "argsort_stable must be 0 or 1");
+    return 0;
+}
+
+void fill_thr_table(const ccdgpu_params &p, double *thr) {
+    for (int k = 0; k <= CCDGPU_MAX_PEEK; ++k) {
+        if (k <= p.peek_size) thr[k] = p.change_threshold;
+        else thr[k] = chi2_5_ppf(1.0 - std::pow(1.0 - p.change_probability, (double)p.peek_size / k));
+    }
+}
+
+int encoded_check(int32_t n_chips, const int32_t *n_pix, const int32_t *n_obs, const uint8_t *enc, int64_t enc_bytes,
+                  bool *packed) {
+    *packed = false;
+    bool mode1 = false;
+    if (!enc || !n_pix || !n_obs || n_chips <= 0) return fail(CCDGPU_EINVAL, "NULL or empty encoded batch");
+    // the encoded batch must describe exactly these chips (the decoder trusts its headers)
+    if (enc_bytes < ccd_enc_table_used(n_chips) || ccd_enc_n_chips(enc) != n_chips)
+        return fail(CCDGPU_EINVAL, "encoded batch: chip table does not match n_chips");
+    const int64_t *off = ccd_enc_chip_off(enc), *pixo = ccd_enc_chip_pix(enc, n_chips);
+    if (off[n_chips] > enc_bytes) return fail(CCDGPU_EINVAL, "encoded batch: longer than enc_bytes");
+    int64_t pb = 0, db = 0;
+    for (int32_t k = 0; k < n_chips; ++k) {
+        if (n_pix[k] <= 0 || n_obs[k] <= 0 || n_obs[k] > CCDGPU_MAX_OBS)
+            return enc_fail(k, " has no pixels / observations");
+        if (off[k] < 0 || off[k] + CCD_ENC_HDR > off[k + 1] || pixo[k] != pb)
+            return fail(CCDGPU_EINVAL, "encoded batch: bad chip table entry " + std::to_string(k));
+        const uint8_t *sec = enc + off[k];
+        const ccd_enc_hdr *h = reinterpret_cast<const ccd_enc_hdr *>(sec);
+        if ((h->mode != CCD_ENC_MODE_RAW && h->mode != CCD_ENC_MODE_COLS && h->mode != CCD_ENC_MODE_PACK) ||
+            h->n_pix != n_pix[k] || h->n_obs != n_obs[k] || h->data_off != db ||
+            (h->mode != CCD_ENC_MODE_RAW && (h->n_pal < 1 || h->n_pal > 16)))
+            return enc_fail(k, " header does not match its shape");
+        // the section holds everything its mode's layout addresses (the decoder trusts it)
+        const int64_t np_ = n_pix[k], plane = np_ * n_obs[k], sec_bytes = off[k + 1] - off[k];
+        const int32_t no_ = n_obs[k];
+        const uint32_t *koff = reinterpret_cast<const uint32_t *>(ccd_enc_koff(sec));
+        int rc;
+        if (h->mode == CCD_ENC_MODE_RAW) {
+            if (sec_bytes < ccd_enc_size_raw(plane)) return enc_fail(k, " raw section is truncated");
+        } else if (h->mode == CCD_ENC_MODE_PACK) {
+            // bit-packed runs: the kept table as in mode 1, then every run's descriptor against the
+            // prefix sums of its code words (ceil(k w / 32)) and exceptions, the totals against the
+            // header, and the section long enough for all five parts and the pad word -- after
+            // this no code bit can send the decoder outside the section
+            *packed = true;
+            const int64_t kept = h->kept, code_words = h->code_words, exc_total = h->exc_total;
+            if (kept < 0 || kept > plane || h->band_stride != 0 || code_words < 0 || exc_total < 0 ||
+                code_words > 4 * plane + 8 * np_ || exc_total > 7 * plane ||
+                sec_bytes < ccd_enc_size_pack_fixed(np_, no_))
+                return enc_fail(k, " packed header does not fit its section");
+            if ((rc = enc_check_koff(k, koff, np_, no_, kept))) return rc;
+            const ccd_enc_run *runs = reinterpret_cast<const ccd_enc_run *>(ccd_enc_body(sec, np_, no_));
+            int64_t cw = 0, ex = 0;
+            for (int64_t r = 0; r < CCD_ENC_BANDS * np_; ++r) {
+                const ccd_enc_run &d = runs[r];
+                const int64_t kk = (int64_t)(koff[r / CCD_ENC_BANDS + 1] - koff[r / CCD_ENC_BANDS]);
+                if (d.w > 16) return enc_fail(k, " run " + std::to_string(r) + " has a width above 16");
+                if ((int64_t)d.code_word != cw || (int64_t)d.exc_off != ex)
+                    return enc_fail(k, " run " + std::to_string(r) + " does not start at the prefix sums");
+                if ((int64_t)d.n_exc > kk)
+                    return enc_fail(k, " run " + std::to_string(r) + " has more exceptions than values");
+                cw += (kk * d.w + 31) / 32;
+                ex += d.n_exc;
+            }
+            if (cw != code_words || ex != exc_total)
+                return enc_fail(k, " run totals do not match code_words / exc_total");
+            if (sec_bytes < ccd_enc_size_pack(np_, no_, code_words, exc_total))
+                return enc_fail(k, " packed section is truncated");
+        } else {
+            mode1 = true;
+            const int64_t kept = h->kept, bstride = h->band_stride;
+            if (kept < 0 || kept > plane || bstride < kept || bstride % 8 != 0 ||
+                sec_bytes < ccd_enc_size_cols(np_, no_, bstride))
+                return enc_fail(k, " band columns do not fit its section");
+            if ((rc = enc_check_koff(k, koff, np_, no_, kept))) return rc;
+        }
+        pb += n_pix[k];
+        db += (int64_t)n_pix[k] * n_obs[k];
+    }
+    if (pixo[n_chips] != pb) return fail(CCDGPU_EINVAL, "encoded batch: pixel total does not match");
+    if (mode1 && *packed) return fail(CCDGPU_EINVAL, "encoded batch: mode 1 and mode 2 sections in one batch");
+    return 0;
+}
+
+// Children have larger indices than their parents, so one pass in index order carries the depth
+// down from the roots.
+int forest_validate(const ccdgpu_forest *f, int32_t *max_depth) {
+    if (!f) return fail(CCDGPU_EINVAL, "forest is NULL");
+    if (f->n_trees < 1) return fail(CCDGPU_EINVAL, "forest: n_trees must be >= 1, got " + std::to_string(f->n_trees));
+    if (f->n_nodes < 1) return fail(CCDGPU_EINVAL, "forest: n_nodes must be >= 1, got " + std::to_string(f->n_nodes));
+    if (f->n_features < 1 || f->n_features > CCDGPU_FOREST_MAX_FEATURES)
+        return fail(CCDGPU_EINVAL, "forest: n_features must be in [1, " + std::to_string(CCDGPU_FOREST_MAX_FEATURES) + "], got " +
+                                       std::to_string(f->n_features));
+    if (f->n_classes < 1 || f->n_classes > CCDGPU_FOREST_MAX_CLASSES)
+        return fail(CCDGPU_EINVAL, "forest: n_classes must be in [1, " + std::to_string(CCDGPU_FOREST_MAX_CLASSES) + "], got " +
+                                       std::to_string(f->n_classes));
+    if (!f->root || !f->feature || !f->threshold || !f->left || !f->right || !f->value)
+        return fail(CCDGPU_EINVAL, "forest: NULL array");
+    const int32_t nn = f->n_nodes, nc = f->n_classes;
+    // depth of a node below its root; -1: not reached from any root; parents counted in `seen`
+    std::vector<int32_t> depth((size_t)nn, -1);
+    std::vector<unsigned char> seen((size_t)nn, 0);
+    for (int32_t t = 0; t < f->n_trees; ++t) {
+        const int32_t r = f->root[t];
+        if (r < 0 || r >= nn)
+            return fail(CCDGPU_EINVAL, "forest: root of tree " + std::to_string(t) + " is " + std::to_string(r) +
+                                           ", outside [0, " + std::to_string(nn) + ")");
+        if (seen[r]) return fail(CCDGPU_EINVAL, "forest: node " + std::to_string(r) + " is the root of two trees (shared node)");
+        seen[r] = 1;
+        depth[r] = 0;
+    }
+    int32_t deepest = 0;
+    for (int32_t n = 0; n < nn; ++n) {
+        if (f->feature[n] < 0) {
+            for (int32_t k = 0; k < nc; ++k)
+                if (!std::isfinite(f->value[(size_t)n * nc + k]))
+                    return fail(CCDGPU_EINVAL, "forest: leaf " + std::to_string(n) + " has a non-finite value (class " +
+                                                   std::to_string(k) + ")");
+            if (depth[n] > deepest) deepest = depth[n];
+            continue;
+        }
+        if (f->feature[n] >= f->n_features)
+            return fail(CCDGPU_EINVAL, "forest: node " + std::to_string(n) + " tests feature " + std::to_string(f->feature[n]) +
+                                           " >= n_features " + std::to_string(f->n_features));
+        if (!std::isfinite(f->threshold[n]))
+            return fail(CCDGPU_EINVAL, "forest: node " + std::to_string(n) + " has a non-finite threshold");
+        const int32_t ch[2] = {f->left[n], f->right[n]};
+        for (int32_t side = 0; side < 2; ++side) {
+            const int32_t c = ch[side];
+            const char *name = side ? "right" : "left";
+            if (c < 0 || c >= nn)
+                return fail(CCDGPU_EINVAL, "forest: " + std::string(name) + " child of node " + std::to_string(n) + " is " +
+                                               std::to_string(c) + ", outside [0, " + std::to_string(nn) + ")");
+            if (c <= n)
+                return fail(CCDGPU_EINVAL, "forest: " + std::string(name) + " child of node " + std::to_string(n) + " is " +
+                                               std::to_string(c) + ", not greater than its parent's index");
+            if (seen[c]) return fail(CCDGPU_EINVAL, "forest: node " + std::to_string(c) + " has two parents (shared node)");
+            seen[c] = 1;
+            if (depth[n] >= 0) depth[c] = depth[n] + 1;
+        }
+    }
+    if (max_depth) *max_depth = deepest;
+    return 0;
+}
+
+int forest_build(const ccdgpu_forest *f, int32_t cap, std::vector<unsigned char> &pool, std::vector<int64_t> &tree_off,
+                 std::vector<int32_t> &chunk_first) {
+    const int32_t nt = f->n_trees, nc = f->n_classes;
+    tree_off.assign((size_t)nt + 1, 0);
+    pool.clear();
+    std::vector<int32_t> order;
+    for (int32_t t = 0; t < nt; ++t) {
+        order.assign(1, f->root[t]);
+        size_t leaves = 0;
+        for (size_t i = 0; i < order.size(); ++i) {
+            const int32_t n = order[i];
+            if (f->feature[n] < 0) {
+                ++leaves;
+            } else {
+                order.push_back(f->left[n]);
+                order.push_back(f->right[n]);
+            }
+        }
+        const size_t n_t = order.size();
+        const size_t bytes = (n_t * sizeof(CcdForestNode) + leaves * nc * sizeof(double) + 15) & ~(size_t)15;
+        if (bytes / 8 >= (size_t)INT32_MAX) return fail(CCDGPU_EINVAL, "forest: tree " + std::to_string(t) + " is too large");
+        const size_t at = pool.size();
+        pool.resize(at + bytes, 0);
+        CcdForestNode *nodes = reinterpret_cast<CcdForestNode *>(pool.data() + at);
+        double *vals = reinterpret_cast<double *>(pool.data() + at);
+        size_t next = 1, leaf = 0;
+        for (size_t i = 0; i < n_t; ++i) {
+            const int32_t n = order[i];
+            if (f->feature[n] < 0) {
+                const size_t v = n_t * sizeof(CcdForestNode) / sizeof(double) + leaf * nc;
+                nodes[i].threshold = 0.0;
+                nodes[i].feature = -1;
+                nodes[i].left = (int32_t)v;
+                std::memcpy(vals + v, f->value + (size_t)n * nc, sizeof(double) * nc);
+                ++leaf;
+            } else {
+                nodes[i].threshold = f->threshold[n];
+                nodes[i].feature = f->feature[n];
+                nodes[i].left = (int32_t)next;
+                next += 2;
+            }
+        }
+        tree_off[t + 1] = (int64_t)pool.size();
+    }
+    chunk_first.assign(1, 0);
+    for (int32_t t = 0; t < nt;) {
+        int32_t e = t + 1;
+        if (tree_off[e] - tree_off[t] <= cap)
+            while (e < nt && tree_off[e + 1] - tree_off[t] <= cap) ++e;
+        chunk_first.push_back(e);
+        t = e;
+    }
+    return 0;
+}
+
+int predict_check_dates(int64_t n_dates, const int64_t *dates, double avg_days_yr) {
+    if (n_dates < 0) return fail(CCDGPU_EINVAL, "predict: n_dates must be >= 0, got " + std::to_string(n_dates));
+    if (n_dates > INT32_MAX) return fail(CCDGPU_EINVAL, "predict: n_dates must be < 2^31, got " + std::to_string(n_dates));
+    if (n_dates > 0 && !dates) return fail(CCDGPU_EINVAL, "predict: dates is NULL");
+    if (!std::isfinite(avg_days_yr) || !(avg_days_yr > 0.0))
+        return fail(CCDGPU_EINVAL, "predict: avg_days_yr must be finite and > 0, got " + std::to_string(avg_days_yr));
+    for (int64_t i = 0; i < n_dates; ++i)
+        if (dates[i] < 1 || dates[i] > CCDGPU_PREDICT_MAX_DATE)
+            return fail(CCDGPU_EINVAL, "predict: dates[" + std::to_string(i) + "] = " + std::to_string(dates[i]) +
+                                           " is outside 1 .. " + std::to_string(CCDGPU_PREDICT_MAX_DATE));
+    return 0;
+}
+
+int predict_check_modes(int32_t cover, int32_t dtype) {
+    if (cover != CCDGPU_COVER_SPAN && cover != CCDGPU_COVER_EXTEND)
+        return fail(CCDGPU_EINVAL, "predict: unknown cover " + std::to_string(cover));
+    if (dtype != CCDGPU_PREDICT_F32 && dtype != CCDGPU_PREDICT_I16)
+        return fail(CCDGPU_EINVAL, "predict: unknown dtype " + std::to_string(dtype));
+    return 0;
+}
+
+}  // namespace ccdhost
+
+using namespace ccdhost;
+
+extern "C" {
+
+const char *ccdgpu_last_error(void) { return g_err.c_str(); }
+
+void ccdgpu_params_default(ccdgpu_params *p) {
+    std::memset(p, 0, sizeof(*p));
+    p->meow_size = 12;
+    p->peek_size = 6;
+    p->day_delta = 365;
+    p->coef_min = 4;
+    p->coef_mid = 6;
+    p->coef_max = 8;
+    p->num_obs_factor = 3;
+    p->detection_bands = 0x3E;
+    p->tmask_bands = 0x12;
+    p->lasso_max_iter = 1000;
+    p->thermal_min = -9320;
+    p->thermal_max = 7070;
+    p->median_green_filter = 400;
+    p->curve_qa_start = 14;
+    p->curve_qa_end = 24;
+    p->curve_qa_insuf_clear = 44;
+    p->curve_qa_persist_snow = 54;
+    p->qa_fill = 0;
+    p->qa_clear = 1;
+    p->qa_water = 2;
+    p->qa_shadow = 3;
+    p->qa_snow = 4;
+    p->qa_cloud = 5;
+    p->qa_cirrus1 = 8;
+    p->qa_cirrus2 = 9;
+    p->qa_occlusion = 10;
+    p->qa_bitpacked = 1;
+    p->adaptive_peek = 1;
+    p->rmse_dof = 0;
+    p->kelvin_to_celsius = 1;
+    p->avg_days_yr = 365.2425;
+    p->change_probability = 0.99;
+    p->change_threshold = 15.086272469388987;
+    p->outlier_threshold = 35.888186879610423;
+    p->t_const = 4.42;
+    p->lasso_alpha = 1.0;
+    p->lasso_tol = 1e-4;
+    p->clear_pct_threshold = 0.25;
+    p->snow_pct_threshold = 0.75;
+    p->argsort_stable = 0;  // numpy quicksort tie order (include/ccdgpu.h)
+    p->reserved0 = 0;
+}
+
+int ccdgpu_encoded_check(int32_t n_chips, const int32_t *n_pix, const int32_t *n_obs, const uint8_t *enc,
+                         int64_t enc_bytes) {
+    bool packed;
+    return encoded_check(n_chips, n_pix, n_obs, enc, enc_bytes, &packed);
+}
+
+int ccdgpu_forest_check(const ccdgpu_forest *f) { return forest_validate(f, nullptr); }
+
+int ccdgpu_forest_depth(const ccdgpu_forest *f, int32_t *max_depth) {
+    if (!max_depth) return fail(CCDGPU_EINVAL, "NULL argument");
+    *max_depth = 0;
+    return forest_validate(f, max_depth);
+}
+
+int ccdgpu_predict_check(int64_t n_pix, const int64_t *row_offsets, int64_t n_rows, const ccdgpu_row *rows, int64_t n_dates,
+                         const int64_t *dates, double avg_days_yr, int32_t cover, int32_t dtype) {
+    if (n_pix < 0) return fail(CCDGPU_EINVAL, "predict: n_pix must be >= 0, got " + std::to_string(n_pix));
+    if (n_rows < 0) return fail(CCDGPU_EINVAL, "predict: n_rows must be >= 0, got " + std::to_string(n_rows));
+    if (!row_offsets) return fail(CCDGPU_EINVAL, "predict: row_offsets is NULL");
+    if (n_rows > 0 && !rows) return fail(CCDGPU_EINVAL, "predict: rows is NULL");
+    if (row_offsets[0] != 0)
+        return fail(CCDGPU_EINVAL, "predict: row_offsets[0] must be 0, got " + std::to_string(row_offsets[0]));
+    for (int64_t p = 0; p < n_pix; ++p)
+        if (row_offsets[p + 1] < row_offsets[p])
+            return fail(CCDGPU_EINVAL, "predict: row_offsets decrease at pixel " + std::to_string(p) + " (" +
+                                           std::to_string(row_offsets[p]) + " -> " + std::to_string(row_offsets[p + 1]) + ")");
+    if (row_offsets[n_pix] != n_rows)
+        return fail(CCDGPU_EINVAL, "predict: row_offsets[n_pix] is " + std::to_string(row_offsets[n_pix]) + ", n_rows is " +
+                                       std::to_string(n_rows));
+    int rc = predict_check_dates(n_dates, dates, avg_days_yr);
+    if (rc) return rc;
+    return predict_check_modes(cover, dtype);
+}
+
+}  // extern "C"

@@ -1,0 +1,52 @@
+// ccdgpu_checks.h -- the host API's error state and the validators of everything a caller hands
+// over (ccdgpu_checks.cpp).  No HIP: this much of the host side also builds with a plain C++
+// compiler, so the checks can run in a stand-alone program under sanitizers
+// (tests/native/host_checks.cpp).
+#pragma once
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "../../include/ccdgpu.h"
+#include "ccd_device.h"
+
+namespace ccdhost {
+
+// records msg as the calling thread's ccdgpu_last_error and returns code
+int fail(int code, const std::string &msg);
+
+// Shape of a staged batch: per-chip pixel / observation counts and their prefix sums
+// (ccd_device.h layout).
+struct Shape {
+    std::vector<int32_t> npix, nobs;
+    std::vector<int64_t> obs_off, pix_off, data_off;  // [n_chips + 1]
+    int32_t n_obs_max = 0;
+    int n_chips() const { return (int)npix.size(); }
+    int64_t total_obs() const { return obs_off.empty() ? 0 : obs_off.back(); }
+    int64_t total_pix() const { return pix_off.empty() ? 0 : pix_off.back(); }
+    int64_t total_data() const { return data_off.empty() ? 0 : data_off.back(); }
+};
+
+int make_shape(int32_t n_chips, const int32_t *n_pix, const int32_t *n_obs, Shape &s);
+int check_params(const ccdgpu_params *p);
+// change threshold per (adaptive) peek size: CcdDetectArgs::thr_table [CCDGPU_MAX_PEEK + 1]
+void fill_thr_table(const ccdgpu_params &p, double *thr);
+
+// ccdgpu_encoded_check (layout: ccd_enc_layout.h); *packed: the batch holds a mode 2 section (it
+// goes to ccd_decode_pack)
+int encoded_check(int32_t n_chips, const int32_t *n_pix, const int32_t *n_obs, const uint8_t *enc, int64_t enc_bytes,
+                  bool *packed);
+
+// The checks of ccdgpu_forest_check, and the forest's depth (branches from a root to its deepest
+// leaf).
+int forest_validate(const ccdgpu_forest *f, int32_t *max_depth);
+// The device form of a checked forest (ccd_device.h): per tree one blob, nodes breadth-first so
+// that the children of a node are adjacent, the leaves' class vectors behind the nodes; then the
+// chunks: runs of whole trees that fit `cap` bytes, a larger tree alone.
+int forest_build(const ccdgpu_forest *f, int32_t cap, std::vector<unsigned char> &pool, std::vector<int64_t> &tree_off,
+                 std::vector<int32_t> &chunk_first);
+
+int predict_check_dates(int64_t n_dates, const int64_t *dates, double avg_days_yr);
+int predict_check_modes(int32_t cover, int32_t dtype);
+
+}  // namespace ccdhost

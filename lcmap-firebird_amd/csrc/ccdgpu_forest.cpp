@@ -1,0 +1,139 @@
+// ccdgpu_forest.cpp -- random-forest classification of segment rows (include/ccdgpu.h; kernels in
+// ccd_forest.hip; the forest's checks and its device form in ccdgpu_checks.cpp).
+#include <algorithm>
+
+#include "ccdgpu_host.h"
+
+using namespace ccdhost;
+
+// rows a classification keeps on the device at a time (the host-matrix path goes slab by slab;
+// a row's result does not depend on its slab)
+static const int64_t FOREST_SLAB = (int64_t)1 << 20;
+
+extern "C" {
+
+int ccdgpu_forest_clear(ccdgpu_ctx *c) {
+    if (!c) return fail(CCDGPU_EINVAL, "NULL ctx");
+    (void)hipSetDevice(c->device);
+    c->has_forest = false;
+    c->forest = CcdForestDev{};
+    c->f_pool.release();
+    c->f_tree_off.release();
+    c->f_chunk_first.release();
+    return 0;
+}
+
+int ccdgpu_forest_set(ccdgpu_ctx *c, const ccdgpu_forest *f) {
+    if (!c) return fail(CCDGPU_EINVAL, "NULL ctx");
+    int32_t max_depth = 0;
+    int rc = forest_validate(f, &max_depth);
+    if (rc) return rc;
+    const int32_t nc = f->n_classes;
+    const int32_t cap = ccdk_forest_chunk_cap(f->n_features);
+    std::vector<unsigned char> pool;
+    std::vector<int64_t> tree_off;
+    std::vector<int32_t> chunk_first;
+    if ((rc = forest_build(f, cap, pool, tree_off, chunk_first))) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->aux));
+    c->has_forest = false;
+    if ((rc = c->f_pool.ensure(pool.size())) || (rc = c->f_tree_off.ensure(tree_off.size())) ||
+        (rc = c->f_chunk_first.ensure(chunk_first.size())))
+        return rc;
+    HIPCHK(hipMemcpy(c->f_pool.p, pool.data(), pool.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(c->f_tree_off.p, tree_off.data(), sizeof(int64_t) * tree_off.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(c->f_chunk_first.p, chunk_first.data(), sizeof(int32_t) * chunk_first.size(), hipMemcpyHostToDevice));
+    for (auto &e : c->f_ev) HIPCHK(e.create());
+    c->forest.pool = c->f_pool.p;
+    c->forest.tree_off = c->f_tree_off.p;
+    c->forest.chunk_first = c->f_chunk_first.p;
+    c->forest.n_chunks = (int32_t)chunk_first.size() - 1;
+    c->forest.n_features = f->n_features;
+    c->forest.n_classes = nc;
+    c->forest.max_depth = max_depth;
+    c->forest.threads = ccdk_forest_threads(f->n_features);
+    c->forest.chunk_cap = cap;
+    c->has_forest = true;
+    return 0;
+}
+
+int ccdgpu_classify(ccdgpu_ctx *c, const double *features, int64_t n_rows, float *rfrawp, double *kernel_seconds) {
+    if (kernel_seconds) *kernel_seconds = 0.0;
+    if (!c) return fail(CCDGPU_EINVAL, "NULL ctx");
+    if (!c->has_forest) return fail(CCDGPU_EINVAL, "no forest set (ccdgpu_forest_set)");
+    int rc = busy(c);
+    if (rc) return rc;
+    if (n_rows < 0) return fail(CCDGPU_EINVAL, "n_rows must be >= 0");
+    if (n_rows == 0) return 0;
+    if (!features || !rfrawp) return fail(CCDGPU_EINVAL, "NULL argument");
+    HIPCHK(hipSetDevice(c->device));
+    const int64_t nf = c->forest.n_features, nc = c->forest.n_classes;
+    const int64_t slab = std::min(n_rows, FOREST_SLAB);
+    if ((rc = c->f_x.ensure((size_t)(slab * nf))) || (rc = c->f_out.ensure((size_t)(slab * nc)))) return rc;
+    hipStream_t ax = c->aux;
+    double secs = 0.0;
+    for (int64_t r0 = 0; r0 < n_rows; r0 += slab) {
+        const int64_t n = std::min(slab, n_rows - r0);
+        HIPCHK(hipMemcpyAsync(c->f_x.p, features + r0 * nf, sizeof(double) * (size_t)(n * nf), hipMemcpyHostToDevice, ax));
+        HIPCHK(hipEventRecord(c->f_ev[0], ax));
+        if (ccdk_forest_classify(&c->forest, c->f_x.p, nullptr, n, c->f_out.p, ax)) {
+            (void)hipStreamSynchronize(ax);
+            return fail(CCDGPU_EHIP, "forest kernel launch failed");
+        }
+        HIPCHK(hipEventRecord(c->f_ev[1], ax));
+        HIPCHK(hipMemcpyAsync(rfrawp + r0 * nc, c->f_out.p, sizeof(float) * (size_t)(n * nc), hipMemcpyDeviceToHost, ax));
+        HIPCHK(hipStreamSynchronize(ax));
+        float ms = 0.f;
+        (void)hipEventElapsedTime(&ms, c->f_ev[0], c->f_ev[1]);
+        secs += ms * 1e-3;
+    }
+    if (kernel_seconds) *kernel_seconds = secs;
+    return 0;
+}
+
+int ccdgpu_classify_rows(ccdgpu_ctx *c, const double *aux, float *rfrawp, int64_t rows_cap, int64_t *n_rows,
+                         double *kernel_seconds) {
+    if (kernel_seconds) *kernel_seconds = 0.0;
+    if (!n_rows) return fail(CCDGPU_EINVAL, "NULL argument");
+    *n_rows = 0;
+    if (!c) return fail(CCDGPU_EINVAL, "NULL ctx");
+    int rc = busy(c);
+    if (rc) return rc;
+    if (!c->ran || c->shape.n_chips() <= 0) return fail(CCDGPU_EINVAL, "no completed run to classify");
+    // the rows of the run, as ccdgpu_fetch_batch_rows_into counts them: max(1, segments) per pixel
+    const int64_t np = c->shape.total_pix();
+    if ((int64_t)c->h_offsets.size() < np + 1) return fail(CCDGPU_EINVAL, "no completed run to classify");
+    int64_t nr = 0;
+    if ((rc = make_row_offsets(c, 0, np, false, &nr))) return rc;
+    *n_rows = nr;
+    if (!c->has_forest) return fail(CCDGPU_EINVAL, "no forest set (ccdgpu_forest_set)");
+    if (c->forest.n_features != 33)
+        return fail(CCDGPU_EINVAL, "classify_rows needs a forest of 33 features (ccdc.features.columns()), this one has " +
+                                       std::to_string(c->forest.n_features));
+    if (rows_cap < nr)
+        return fail(CCDGPU_EINVAL, "classify_rows: buffer too small (need " + std::to_string(nr) + " rows)");
+    if (!aux || !rfrawp) return fail(CCDGPU_EINVAL, "NULL argument");
+    HIPCHK(hipSetDevice(c->device));
+    const int64_t nc = c->forest.n_classes;
+    const int64_t s0 = c->h_offsets[0], n_seg = c->h_offsets[np] - s0;
+    if ((rc = c->f_aux.ensure((size_t)np * 5)) || (rc = c->f_x.ensure((size_t)nr * 33)) || (rc = c->f_skip.ensure((size_t)nr)) ||
+        (rc = c->f_out.ensure((size_t)(nr * nc))) || (rc = make_row_offsets(c, 0, np, true, &nr)))
+        return rc;
+    hipStream_t ax = c->aux;
+    HIPCHK(hipMemcpyAsync(c->f_aux.p, aux, sizeof(double) * (size_t)np * 5, hipMemcpyHostToDevice, ax));
+    HIPCHK(hipEventRecord(c->f_ev[0], ax));
+    if (ccdk_forest_gather(c->csr.p + s0, c->seg_off1.p, c->row_off.p, c->f_aux.p, np, n_seg, nr, c->f_x.p, c->f_skip.p, ax) ||
+        ccdk_forest_classify(&c->forest, c->f_x.p, c->f_skip.p, nr, c->f_out.p, ax)) {
+        (void)hipStreamSynchronize(ax);
+        return fail(CCDGPU_EHIP, "forest kernel launch failed");
+    }
+    HIPCHK(hipEventRecord(c->f_ev[1], ax));
+    HIPCHK(hipMemcpyAsync(rfrawp, c->f_out.p, sizeof(float) * (size_t)(nr * nc), hipMemcpyDeviceToHost, ax));
+    HIPCHK(hipStreamSynchronize(ax));
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, c->f_ev[0], c->f_ev[1]);
+    if (kernel_seconds) *kernel_seconds = ms * 1e-3;
+    return 0;
+}
+
+}  // extern "C"

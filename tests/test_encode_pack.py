@@ -288,3 +288,27 @@ def test_native_round_trip_under_sanitizers(tmp_path):
                              capture_output=True, text=True)
         assert out.returncode == 0, out.stdout + out.stderr
         assert out.stdout.strip().endswith('ok'), out.stdout
+
+
+def test_native_host_checks_under_sanitizers(tmp_path):
+    """tests/native/host_checks.cpp: the host API's validators (csrc/ccdgpu_checks.cpp, no HIP in
+    it) and the encoder in one stand-alone program built with -fsanitize=address,undefined --
+    ccdgpu_encoded_check accepts the encoder's batches (modes 0, 1 and 2) from a heap block of
+    exactly their size and refuses every strict prefix from a block of exactly its size; the
+    forest checks and forest_build on a hand-made forest; make_shape and check_params."""
+    csrc = os.path.join(ROOT, 'lcmap-firebird_amd', 'csrc')
+    san = ['-fsanitize=address,undefined', '-fno-sanitize-recover=undefined']
+    inc = ['-I', os.path.join(ROOT, 'include')]
+    probe = subprocess.run(['gcc', '-fsanitize=address,undefined', '-x', 'c', '-o', str(tmp_path / 'probe'), '-'],
+                           input='int main(void){return 0;}', capture_output=True, text=True)
+    if probe.returncode != 0:
+        pytest.skip('the compiler cannot link -fsanitize=address,undefined')
+    enc_o, exe = str(tmp_path / 'ccd_encode.o'), str(tmp_path / 'host_checks')
+    subprocess.run(['gcc', '-O1', '-g', '-fopenmp', '-c'] + san + inc + ['-o', enc_o, os.path.join(csrc, 'ccd_encode.c')],
+                   check=True)
+    subprocess.run(['g++', '-O1', '-g', '-std=c++17', '-fopenmp'] + san + inc +
+                   ['-o', exe, os.path.join(HERE, 'native', 'host_checks.cpp'), os.path.join(csrc, 'ccdgpu_checks.cpp'), enc_o],
+                   check=True)
+    out = subprocess.run([exe], env=dict(os.environ, ASAN_OPTIONS='detect_leaks=1'), capture_output=True, text=True)
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert out.stdout.strip().endswith('ok'), out.stdout

@@ -312,3 +312,94 @@ def test_guard_lines_build_trips_no_guard_and_matches_product():
         assert r.returncode == 0, (lib, r.stderr[-2000:])
         outs.append(r.stdout.strip().splitlines()[-1])
     assert outs[0] == outs[1]
+
+
+def test_synchronize_diag_counters_and_numa_node(ctx):
+    """The entry points no other test calls, after one 1-chip, 4-pixel, 40-date detection:
+    ccdgpu_synchronize returns, ccdgpu_diag_counters gives the statistics words of that run (the
+    first three are what ccdgpu_last_stats reports), ccdgpu_device_numa_node a node or -1."""
+    cfg = synth.config(5)
+    d, s, q = synth.chip(cfg, 3, 0, 4, chip_dates=synth.dates(cfg, 3)[:40])
+    ctx.detect_batch(d, s, q)
+    ctx.synchronize()
+    dc, st = ctx.diag_counters(), ctx.stats()
+    assert len(dc) == 48 and st['pixels'] == 4
+    assert dc[:3] == [st['lasso_fits'], st['cd_sweeps'], st['flops']]
+    node = ccdgpu.device_numa_node(0)
+    assert isinstance(node, int) and node >= -1
+
+
+_LIFETIME_SCRIPT = r'''
+import ctypes, sys
+sys.path[:0] = sys.argv[1:]
+import numpy as np
+import ccdgpu
+from ccdgpu import abi, synth
+
+ARG_SLOTS = 16  # CCD_ARG_SLOTS, csrc/ccd_device.h
+cfg = synth.config(5)
+d, s, q = synth.chip(cfg, 3, 0, 4, chip_dates=synth.dates(cfg, 3)[:40])
+assert q.shape == (4, 40)
+cx, cy = np.array([3000], np.int32), np.array([-6000], np.int32)
+
+
+def chain(c):
+    """one detection through the slot and the batch chain"""
+    b = ccdgpu.ChipBatch.from_chips([(d, s, q)], pinned=True)
+    bufs = ccdgpu.RowsBuffers()
+    c.stage_slot_chips(0, b)
+    c.run_slot_begin_rows(0, cx, cy, bufs)
+    off, rows, mask = c.run_slot_end_rows()
+    return off.copy(), rows.copy(), mask.copy()
+
+
+ctxs = [ccdgpu.Context(0) for _ in range(ARG_SLOTS)]
+try:
+    ccdgpu.Context(0)
+except ccdgpu.CcdGpuError as e:
+    assert 'live contexts' in str(e), str(e)
+else:
+    raise AssertionError('context %d was opened' % (ARG_SLOTS + 1))
+# a closed context's launch-argument slot comes back (through the context's destructor)
+ctxs.pop(5).close()
+new = ccdgpu.Context(0)
+ctxs.append(new)
+got = chain(new)
+# the same chip by detect_batch and the batch fetch (C level: the wrapper's fetch_batch_rows
+# wants a staged ChipBatch) on another of the open contexts
+other = ctxs[0]
+u = other.detect_batch(d, s, q)
+r = abi.Rows()
+rc = ccdgpu.lib().ccdgpu_fetch_batch_rows(other._ctx, cx.ctypes.data, cy.ctypes.data, 100, ctypes.byref(r))
+assert rc == 0, ccdgpu.last_error()
+ref = abi.unpack_rows(r)
+ccdgpu.lib().ccdgpu_rows_free(ctypes.byref(r))
+assert ref[1].shape[0] == int(np.maximum(1, np.diff(u.seg_offsets)).sum())  # max(1, segments) rows per pixel
+assert np.array_equal(got[0], ref[0]) and got[1].tobytes() == ref[1].tobytes() and np.array_equal(got[2], ref[2])
+for c in ctxs:
+    c.close()
+# and from nothing again: open, detect, close
+for _ in range(2):
+    c = ccdgpu.Context(0)
+    again = chain(c)
+    c.close()
+    assert again[1].tobytes() == ref[1].tobytes() and np.array_equal(again[2], ref[2])
+print('ok %d rows' % ref[1].shape[0])
+'''
+
+
+def test_context_lifetime_and_argument_slots():
+    """CCD_ARG_SLOTS contexts open at once and one more is refused ('live contexts'); closing one
+    frees its slot for a new context, which detects a 1-chip, 4-pixel, 40-date batch through
+    stage_slot_chips / run_slot_begin_rows / run_slot_end_rows with the rows and mask that
+    detect_batch and the batch fetch give on another open context; after all are closed, two more
+    open-detect-close rounds give the same.  Everything a context owns is released by its
+    destructor, so this is the test that a buffer, event or slot is not lost there.  In a child
+    process: the slot table is per process, and this one holds contexts of its own."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    paths = [os.path.join(root, 'lcmap-firebird_amd'), os.path.join(root, 'tests')]
+    r = subprocess.run([sys.executable, '-c', _LIFETIME_SCRIPT] + paths, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-2000:])
+    assert r.stdout.strip().splitlines()[-1].startswith('ok')
