@@ -464,6 +464,101 @@ int ccdgpu_predict_rows(ccdgpu_ctx *ctx, int32_t chip, int64_t n_dates, const in
  * coefficient_matrix(dates, avg_days_yr, 8) -- which is what makes exact tests of the rule possible. */
 int ccdgpu_coefficient_matrix(ccdgpu_ctx *ctx, int64_t n_dates, const int64_t *dates, double avg_days_yr, double *basis);
 
+/* Annual change and land-cover product rasters from segments: per pixel and product date (LCMAP's
+ * are the 1 July of each year) the time of spectral change, the change magnitude, the time since the
+ * last change, the spectral stability period, the model quality, the primary and secondary land
+ * cover with their confidences and the annual land-cover change.  The reference ecosystem's product
+ * generator (lcmap-gaia) is not pinned here, so parity with it is not claimed: the rule below is
+ * normative, and where gaia's choice is not certain it is a parameter (bot, mag_bands, cover, labels).
+ *
+ * The rule.  A pixel's rows are ccdgpu_row records in table order; `dates` [n_dates] are proleptic
+ * ordinals shared by the pixels of the call, in any order, repeats allowed.  For a date t, a(t) is the
+ * ordinal of 1 January of t's proleptic-Gregorian calendar year and b(t) that of the next 1 January
+ * (ccdgpu_year_window; integer arithmetic on the host).  A row is a MODEL iff has_model != 0; it is a
+ * BREAK iff it is a model, chprob == 1.0f and bday >= 1.  Day comparisons are on integers.
+ * Change products, per pixel and date index i with date t:
+ *   sctime  uint16  the first break in table order with a(t) <= bday < b(t): bday - a(t) + 1 (the day
+ *                   of the year, 1 .. 366); no such break: 0
+ *   scmag   float   of that same row: s = 0.0; for band b = 0 .. 6 with bit b of mag_bands set, in this
+ *                   order, m = (double)mag[b], s = s + m * m (the product and the sum each rounded on
+ *                   its own); the value is (float)sqrt(s), sqrt correctly rounded and the narrowing
+ *                   to nearest; a NaN result is the quiet NaN 0x7fc00000; no such row: 0.0f
+ *   sclast  uint16  min(t - g, 65535), g the greatest bday over breaks with bday <= t; no such break: 0
+ *   scstab  uint16  min(t - g, 65535), g the greatest value over all models of sday (when sday <= t)
+ *                   and, for breaks, bday (when bday <= t); none: min(t - bot, 65535) if t >= bot,
+ *                   else 0
+ *   scmqa   uint8   curqa, clamped to 0 .. 255, of the first model in table order with
+ *                   sday <= t <= eday; none: 0
+ * Cover products need rfrawp [n_rows][n_classes] float, row-aligned with the rows, n_classes >= 1:
+ *   the row r of (pixel, t) is the one the prediction's rule takes under `cover` (CCDGPU_COVER_SPAN /
+ *   CCDGPU_COVER_EXTEND).  The cover products are UNDEFINED when there is no such row, when any of
+ *   rfrawp[r][0 .. n_classes) is NaN, or when S -- the sum of the values widened to double, in class
+ *   order, each add rounded -- is not a finite value above 0.  Otherwise i1 is the index of the
+ *   largest value, ties going to the lowest index, and i2 the same with i1 excluded (none when
+ *   n_classes == 1).
+ *   lcpri   uint8   labels[i1]; undefined: 0
+ *   lcsec   uint8   labels[i2]; undefined or no i2: 0
+ *   lcpconf uint8   rint(100.0 * (double)rfrawp[r][i1] / S) clamped to 0 .. 100 (the product and the
+ *                   quotient each rounded on its own, halves to even); undefined: 0
+ *   lcsconf uint8   the same with i2; undefined or no i2: 0
+ *   lcachg  uint16  date index 0: 0; i > 0: with c = lcpri at date index i and q = lcpri at date index
+ *                   i - 1, in the order the dates were given, q * 256 + c when both are non-zero and
+ *                   differ, else 0 (whether or not lcpri itself is requested)
+ * Every product is an array [n_dates][n_pix]: date-major, pixel-contiguous, each date one raster plane
+ * in pixel order (a 100 x 100 chip's plane is its raster).  A NULL pointer in struct ccdgpu_products: that
+ * product is not wanted.  A value does not depend on how pixels are batched, slabbed or launched; a
+ * restatement of these lines in numpy is bit-equal. */
+typedef struct ccdgpu_product_params {
+    int64_t bot;                /* 723546   the beginning of time, 1982-01-01 (scstab)            */
+    uint32_t mag_bands;         /* 0x3E     bit mask, green .. swir2: the detection bands (scmag) */
+    int32_t cover;              /* CCDGPU_COVER_EXTEND                                            */
+    int32_t n_classes;          /* 0 .. 32; 0: no cover products                                  */
+    uint8_t labels[32];         /* k + 1    product value of class k, 1 .. 255                    */
+    int32_t reserved0;          /* 0                                                              */
+} ccdgpu_product_params;
+void ccdgpu_product_params_default(ccdgpu_product_params *p);
+/* the ten outputs (no typedef: the tag shares its name with the function below) */
+struct ccdgpu_products {
+    uint16_t *sctime;
+    float *scmag;
+    uint16_t *sclast, *scstab;
+    uint8_t *scmqa;
+    uint8_t *lcpri, *lcsec, *lcpconf, *lcsconf;
+    uint16_t *lcachg;
+};
+/* a(t) and b(t) of the rule for t in 1 .. CCDGPU_PREDICT_MAX_DATE (else CCDGPU_EINVAL); host only. */
+int ccdgpu_year_window(int64_t t, int64_t *a, int64_t *b);
+/* The checks a product request passes before anything reaches the device (no device needed): every
+ * check ccdgpu_predict_check makes on counts, offsets and dates, and CCDGPU_EINVAL with the reason
+ * for: params or out NULL; bot outside 1 .. CCDGPU_PREDICT_MAX_DATE; mag_bands with bits above 6;
+ * n_classes outside 0 .. 32; a label of 0 among the first n_classes; an unknown cover; a cover output
+ * requested with rfrawp == NULL or n_classes == 0; all ten outputs NULL. */
+int ccdgpu_products_check(int64_t n_pix, const int64_t *row_offsets, int64_t n_rows, const ccdgpu_row *rows,
+                          const float *rfrawp, int64_t n_dates, const int64_t *dates, const ccdgpu_product_params *params,
+                          const struct ccdgpu_products *out);
+/* Host-table path: pixel p has rows[row_offsets[p] .. row_offsets[p + 1]) and, with rfrawp, their
+ * rfrawp rows.  Runs the check first (n_rows = row_offsets[n_pix]); synchronous; *kernel_seconds (may
+ * be NULL) gets the device time of the kernels.  n_pix == 0 or n_dates == 0 succeeds without a launch.
+ * The output is produced on the device in slabs of whole pixels (at most 256 MiB of device output, or
+ * CCDGPU_PRODUCT_SLAB_PIXELS pixels from the environment, a test knob), each requested product of a
+ * slab copied back with one strided copy.  Refused with CCDGPU_EINVAL while a detection begun with
+ * ccdgpu_run_slot_begin is not finished. */
+int ccdgpu_products(ccdgpu_ctx *ctx, int64_t n_pix, const int64_t *row_offsets, const ccdgpu_row *rows, const float *rfrawp,
+                    int64_t n_dates, const int64_t *dates, const ccdgpu_product_params *params,
+                    const struct ccdgpu_products *out, double *kernel_seconds);
+/* Chained path: the same for the pixels of chip `chip` of the context's last completed run, from its
+ * segments on the device -- magnitude and change_probability narrowed to float32 exactly as the row
+ * packer does, every segment a model -- so the output equals ccdgpu_products' on the rows
+ * ccdgpu_fetch_rows gives for that chip.  rfrawp (may be NULL) holds that chip's rows in
+ * ccdgpu_fetch_rows / ccdgpu_classify_rows order, pyccd.default's row of a pixel without segments
+ * included.  Preconditions and error codes as ccdgpu_predict_rows. */
+int ccdgpu_products_rows(ccdgpu_ctx *ctx, int32_t chip, const float *rfrawp, int64_t n_dates, const int64_t *dates,
+                         const ccdgpu_product_params *params, const struct ccdgpu_products *out, double *kernel_seconds);
+/* The number of rows ccdgpu_fetch_rows gives for chip `chip` of the last completed run -- what the
+ * rfrawp of ccdgpu_products_rows must hold, and where the chip's rows lie among the batch's of
+ * ccdgpu_classify_rows (chips in order) -- from the host's copy of the segment offsets: no device work. */
+int ccdgpu_chip_row_count(ccdgpu_ctx *ctx, int32_t chip, int64_t *n_rows);
+
 /* Kernel statistics of the last run (per launch of the main detection kernel). */
 typedef struct ccdgpu_stats {
     double detect_ms;           /* average duration of the detection kernel (HIP events)   */

@@ -60,11 +60,17 @@ def rows_from_table(segments):
     [n_pixels + 1], rows abi.ROW_DTYPE [n_rows]): a pixel's rows together, in table order.  ISO days
     become ordinals (a null bday 0); a null chprob marks pyccd.default's row, has_model 0, whose null
     columns become 0."""
+    return rows_order_from_table(segments)[:3]
+
+
+def rows_order_from_table(segments):
+    """``rows_from_table`` with, fourth, the table row each returned row came from (int64 [n_rows]):
+    what brings a column of the table that is not part of the rows -- rfrawp -- into their order."""
     from ccdgpu import abi
     n = segments.num_rows
     rows = np.zeros(n, dtype=abi.ROW_DTYPE)
     if n == 0:
-        return np.zeros((0, 4), dtype=np.int32), np.zeros(1, dtype=np.int64), rows
+        return np.zeros((0, 4), dtype=np.int32), np.zeros(1, dtype=np.int64), rows, np.zeros(0, dtype=np.int64)
     key = np.stack([_column(segments, k, np.int32) for k in ('cx', 'cy', 'px', 'py')], axis=1)
     rows['px'], rows['py'] = key[:, 2], key[:, 3]
     for k in _DAY_COLS:
@@ -93,7 +99,7 @@ def rows_from_table(segments):
     pixel = rank[inverse.reshape(-1)]
     order = np.argsort(pixel, kind='stable')
     offsets = np.concatenate([[0], np.cumsum(np.bincount(pixel, minlength=uniq.shape[0]))]).astype(np.int64)
-    return key[np.sort(first)], offsets, rows[order]
+    return key[np.sort(first)], offsets, rows[order], order
 
 
 def _context(context):

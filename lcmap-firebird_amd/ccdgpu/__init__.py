@@ -107,6 +107,21 @@ def _declare(L):
     L.ccdgpu_predict_rows.restype = c.c_int
     L.ccdgpu_coefficient_matrix.argtypes = [c.c_void_p, c.c_int64, c.c_void_p, c.c_double, c.c_void_p]
     L.ccdgpu_coefficient_matrix.restype = c.c_int
+    L.ccdgpu_product_params_default.argtypes = [c.POINTER(abi.ProductParams)]
+    L.ccdgpu_product_params_default.restype = None
+    L.ccdgpu_year_window.argtypes = [c.c_int64, c.POINTER(c.c_int64), c.POINTER(c.c_int64)]
+    L.ccdgpu_year_window.restype = c.c_int
+    L.ccdgpu_products_check.argtypes = [c.c_int64, c.c_void_p, c.c_int64, c.c_void_p, c.c_void_p, c.c_int64, c.c_void_p,
+                                        c.POINTER(abi.ProductParams), c.POINTER(abi.Products)]
+    L.ccdgpu_products_check.restype = c.c_int
+    L.ccdgpu_products.argtypes = [c.c_void_p, c.c_int64, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64, c.c_void_p,
+                                  c.POINTER(abi.ProductParams), c.POINTER(abi.Products), c.POINTER(c.c_double)]
+    L.ccdgpu_products.restype = c.c_int
+    L.ccdgpu_products_rows.argtypes = [c.c_void_p, c.c_int32, c.c_void_p, c.c_int64, c.c_void_p, c.POINTER(abi.ProductParams),
+                                       c.POINTER(abi.Products), c.POINTER(c.c_double)]
+    L.ccdgpu_products_rows.restype = c.c_int
+    L.ccdgpu_chip_row_count.argtypes = [c.c_void_p, c.c_int32, c.POINTER(c.c_int64)]
+    L.ccdgpu_chip_row_count.restype = c.c_int
     L.ccdgpu_detect_batch.argtypes = [c.c_void_p, c.POINTER(abi.Params), c.c_int32, c.c_int32,
                                       c.c_void_p, c.c_void_p, c.c_void_p, c.POINTER(abi.Result)]
     L.ccdgpu_result_free.argtypes = [c.POINTER(abi.Result)]
@@ -154,7 +169,9 @@ EXPORTS = ('ccdgpu_version', 'ccdgpu_last_error', 'ccdgpu_params_default', 'ccdg
            'ccdgpu_run_slot_begin_rows', 'ccdgpu_run_slot_end_rows', 'ccdgpu_encoded_check',
            'ccdgpu_forest_check', 'ccdgpu_forest_depth', 'ccdgpu_forest_set', 'ccdgpu_forest_clear',
            'ccdgpu_classify', 'ccdgpu_classify_rows', 'ccdgpu_encoded_bound_flags', 'ccdgpu_encode_chips_flags',
-           'ccdgpu_predict_check', 'ccdgpu_predict', 'ccdgpu_predict_rows', 'ccdgpu_coefficient_matrix')
+           'ccdgpu_predict_check', 'ccdgpu_predict', 'ccdgpu_predict_rows', 'ccdgpu_coefficient_matrix',
+           'ccdgpu_product_params_default', 'ccdgpu_year_window', 'ccdgpu_products_check', 'ccdgpu_products',
+           'ccdgpu_products_rows', 'ccdgpu_chip_row_count')
 
 
 def lib():
@@ -488,6 +505,110 @@ def predict_check(row_offsets, rows, dates, avg_days_yr=365.2425, cover=0, dtype
     ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
     if lib().ccdgpu_predict_check(int(n_pix), ptr(off), int(n_rows), ptr(r), int(n_dates), ptr(d), float(avg_days_yr),
                                   int(cover), int(dtype)) != 0:
+        raise ValueError(last_error())
+
+
+def year_window(dates):
+    """(a, b) int64 arrays: the ordinals of 1 January of each date's calendar year and of the next
+    1 January (ccdgpu_year_window; no device needed).  Raises ValueError for a date outside
+    1 .. abi.PREDICT_MAX_DATE."""
+    d = _predict_dates(dates)
+    a, b = np.empty_like(d), np.empty_like(d)
+    L = lib()
+    x, y = ctypes.c_int64(0), ctypes.c_int64(0)
+    for i, t in enumerate(d.tolist()):
+        if L.ccdgpu_year_window(t, ctypes.byref(x), ctypes.byref(y)) != 0:
+            raise ValueError(last_error())
+        a[i], b[i] = x.value, y.value
+    return a, b
+
+
+def product_params(bot=None, mag_bands=None, cover='extend', n_classes=0, labels=None):
+    """abi.ProductParams from the library's defaults (ccdgpu_product_params_default) and what is given:
+    cover 'span' / 'extend' (or the code), labels the product values of the classes (default k + 1;
+    n_classes then defaults to their number)."""
+    p = abi.ProductParams()
+    lib().ccdgpu_product_params_default(ctypes.byref(p))
+    if bot is not None:
+        p.bot = int(bot)
+    if mag_bands is not None:
+        p.mag_bands = int(mag_bands)
+    p.cover = _predict_modes(cover, abi.PREDICT_F32)[0]
+    if labels is not None:
+        labels = [int(v) for v in labels]
+        if len(labels) > abi.PRODUCT_MAX_CLASSES or any(not 0 <= v <= 255 for v in labels):
+            raise ValueError('labels must be at most %d values in 0 .. 255' % abi.PRODUCT_MAX_CLASSES)
+        for k, v in enumerate(labels):
+            p.labels[k] = v
+        if not n_classes:
+            n_classes = len(labels)
+    p.n_classes = int(n_classes)
+    return p
+
+
+def _product_request(want, out, n_pix, n_dates, cover_ok):
+    """(names, arrays dict, abi.Products) of a product request: ``want`` names (None: the change
+    products, and the cover products when there is an rfrawp), ``out`` an optional dict of arrays
+    [n_dates][n_pix] to fill instead of new ones."""
+    if want is None:
+        want = abi.CHANGE_PRODUCTS + (abi.COVER_PRODUCTS if cover_ok else ())
+    want = (want,) if isinstance(want, str) else tuple(want)
+    for name in want:
+        if name not in abi.PRODUCT_DTYPES:
+            raise ValueError('unknown product %r (one of %s)' % (name, ', '.join(n for n, _ in abi.PRODUCTS)))
+    arrays, ptrs = {}, abi.Products()
+    for name, typ in abi.PRODUCTS:
+        if name not in want:
+            continue
+        a = None if out is None else out.get(name)
+        if a is None:
+            a = np.empty((n_dates, n_pix), dtype=typ)
+        elif (not isinstance(a, np.ndarray) or a.shape != (n_dates, n_pix) or a.dtype != np.dtype(typ) or
+              not a.flags.c_contiguous or not a.flags.writeable):
+            raise ValueError('out[%r] must be a writeable C-contiguous %s array of shape %r'
+                             % (name, np.dtype(typ).name, (n_dates, n_pix)))
+        arrays[name] = a
+        setattr(ptrs, name, a.ctypes.data)
+    return want, arrays, ptrs
+
+
+def _rfrawp(rfrawp, n_rows, params):
+    """rfrawp as float32 [n_rows][n_classes] (n_classes of the params set from it when 0), or None."""
+    if rfrawp is None:
+        return None
+    r = np.ascontiguousarray(rfrawp, dtype=np.float32)
+    if r.ndim != 2 or r.shape[0] != n_rows:
+        raise ValueError('rfrawp must be [%d][n_classes], got %r' % (n_rows, r.shape))
+    if params.n_classes == 0:
+        params.n_classes = r.shape[1]
+    if r.shape[1] != params.n_classes:
+        raise ValueError('rfrawp has %d classes, the parameters %d' % (r.shape[1], params.n_classes))
+    return r
+
+
+def products_check(row_offsets, rows, dates, rfrawp=None, params=None, want=abi.CHANGE_PRODUCTS, n_pix=None, n_rows=None):
+    """ccdgpu_products_check (no device needed) over array-likes; None passes a NULL pointer (for
+    ``params`` the defaults), n_pix / n_rows default to the arrays' sizes; ``want`` names the outputs
+    that are requested (as non-NULL pointers that are not written).  Raises ValueError with the
+    library's message."""
+    off = None if row_offsets is None else np.ascontiguousarray(row_offsets, dtype=np.int64).reshape(-1)
+    r = None if rows is None else np.ascontiguousarray(rows, dtype=abi.ROW_DTYPE).reshape(-1)
+    d = None if dates is None else _predict_dates(dates)
+    rf = None if rfrawp is None else np.ascontiguousarray(rfrawp, dtype=np.float32)
+    if n_pix is None:
+        n_pix = 0 if off is None else off.shape[0] - 1
+    if n_rows is None:
+        n_rows = 0 if r is None else r.shape[0]
+    n_dates = 1 if d is None else d.shape[0]  # (a NULL date vector of no dates is fine: ask for one)
+    if off is not None and off.shape[0] < n_pix + 1:
+        raise ValueError('row_offsets has %d entries, n_pix + 1 is %d' % (off.shape[0], n_pix + 1))
+    p = product_params() if params is None else params
+    ptrs = abi.Products()
+    for name in want:
+        setattr(ptrs, name, 1)
+    ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+    if lib().ccdgpu_products_check(int(n_pix), ptr(off), int(n_rows), ptr(r), ptr(rf), int(n_dates), ptr(d),
+                                   None if params is False else ctypes.byref(p), ctypes.byref(ptrs)) != 0:
         raise ValueError(last_error())
 
 
@@ -946,6 +1067,76 @@ class Context(object):
                                          out.ctypes.data, None if idx is None else idx.ctypes.data, ctypes.byref(secs)))
         self.predict_seconds = secs.value
         return out, idx
+
+    # annual change and land-cover product rasters from segments ------------------------------------
+    def products(self, row_offsets, rows, dates, rfrawp=None, params=None, want=None, out=None, **kw):
+        """Product rasters of a host table of segment rows at ``dates`` (ccdgpu_products; the rule is in
+        include/ccdgpu.h): pixel p has rows[row_offsets[p]:row_offsets[p + 1]] (abi.ROW_DTYPE), rfrawp
+        float32 [n_rows][n_classes] is row-aligned with them (None: no cover products).  ``params`` an
+        abi.ProductParams, or the keywords of ``product_params`` (bot, mag_bands, cover, n_classes,
+        labels).  Returns {name: array [n_dates][n_pix]} for the names in ``want`` (abi.PRODUCTS; None:
+        the change products, and the cover products when there is an rfrawp); ``out`` may map names to
+        arrays to fill instead of new ones (page-locked ones, ``pinned_empty``, receive them by DMA).
+        The kernel seconds are in ``products_seconds``.  Arguments that fail ccdgpu_products_check
+        raise CcdGpuError (E_INVAL) with the library's message."""
+        off = np.ascontiguousarray(row_offsets, dtype=np.int64).reshape(-1)
+        r = np.ascontiguousarray(rows, dtype=abi.ROW_DTYPE).reshape(-1)
+        if off.shape[0] < 1:
+            raise ValueError('row_offsets must have n_pix + 1 entries')
+        if int(off[-1]) != r.shape[0]:
+            raise ValueError('row_offsets end at %d, the table has %d rows' % (int(off[-1]), r.shape[0]))
+        d = _predict_dates(dates)
+        p = product_params(**kw) if params is None else params
+        rf = _rfrawp(rfrawp, r.shape[0], p)
+        want, arrays, ptrs = _product_request(want, out, off.shape[0] - 1, d.shape[0], rf is not None)
+        secs = ctypes.c_double(0.0)
+        _check(lib().ccdgpu_products(self._ctx, off.shape[0] - 1, off.ctypes.data, r.ctypes.data,
+                                     None if rf is None else rf.ctypes.data, d.shape[0], d.ctypes.data, ctypes.byref(p),
+                                     ctypes.byref(ptrs), ctypes.byref(secs)))
+        self.products_seconds = secs.value
+        return arrays
+
+    def products_rows(self, chip, dates, rfrawp=None, params=None, want=None, out=None, **kw):
+        """``products`` for the pixels of chip ``chip`` of the last completed run, from its segments on
+        the device (ccdgpu_products_rows): the bytes ``products`` gives on ``fetch_rows(chip, ..)``.
+        rfrawp: that chip's rows of ``classify_rows``, in ``fetch_rows`` order (None: no cover
+        products); its row count is checked by the library's offsets, so pass exactly the chip's."""
+        d = _predict_dates(dates)
+        p = product_params(**kw) if params is None else params
+        batch = getattr(self, '_keep', None)
+        chip = int(chip)
+        if isinstance(batch, ChipBatch):
+            n_pix = int(batch.n_pix[chip]) if 0 <= chip < batch.n_chips else None
+        else:
+            n_pix = getattr(self, '_n_pix', None)
+        secs = ctypes.c_double(0.0)
+        rf = None
+        if rfrawp is not None:
+            rf = np.ascontiguousarray(rfrawp, dtype=np.float32)
+            rf = _rfrawp(rf, rf.shape[0], p)
+        if n_pix is None:  # nothing staged here, or no such chip: the library names the reason (no buffers passed)
+            ptrs = abi.Products()
+            ptrs.sctime = 1
+            _check(lib().ccdgpu_products_rows(self._ctx, chip, None, 0, None, ctypes.byref(p), ctypes.byref(ptrs),
+                                              ctypes.byref(secs)))
+            raise CcdGpuError(abi.E_INVAL, 'no completed run to make products from')
+        want, arrays, ptrs = _product_request(want, out, n_pix, d.shape[0], rf is not None)
+        if rf is not None:  # the chip's rows: a row per segment, one for a pixel without any
+            n_rows = self.chip_row_count(chip)
+            if rf.shape[0] != n_rows:
+                raise ValueError('rfrawp has %d rows, chip %d has %d' % (rf.shape[0], chip, n_rows))
+        _check(lib().ccdgpu_products_rows(self._ctx, chip, None if rf is None else rf.ctypes.data, d.shape[0], d.ctypes.data,
+                                          ctypes.byref(p), ctypes.byref(ptrs), ctypes.byref(secs)))
+        self.products_seconds = secs.value
+        return arrays
+
+    def chip_row_count(self, chip):
+        """Rows ``fetch_rows`` gives for chip ``chip`` of the last completed run (a row per segment, one
+        for a pixel without any): the chip's share of ``classify_rows``' rows, chips in order
+        (ccdgpu_chip_row_count; no device work)."""
+        n = ctypes.c_int64(0)
+        _check(lib().ccdgpu_chip_row_count(self._ctx, int(chip), ctypes.byref(n)))
+        return n.value
 
     def diag_counters(self):
         buf = (ctypes.c_uint64 * 48)()

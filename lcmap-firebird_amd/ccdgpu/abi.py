@@ -21,6 +21,15 @@ PREDICT_FILL_I16 = -9999         # the int16 fill (ARD's); the float32 fill is N
 PREDICT_CACHE_ROWS = 16          # CCD_PREDICT_CACHE_ROWS (csrc/ccd_predict.h): models a block keeps in LDS at a time
 COVERS = {'span': COVER_SPAN, 'extend': COVER_EXTEND}
 PREDICT_DTYPES = {'float32': PREDICT_F32, 'int16': PREDICT_I16}
+# product rasters (ccdgpu_products): names in the order of struct ccdgpu_products, with their types
+PRODUCTS = (('sctime', np.uint16), ('scmag', np.float32), ('sclast', np.uint16), ('scstab', np.uint16), ('scmqa', np.uint8),
+            ('lcpri', np.uint8), ('lcsec', np.uint8), ('lcpconf', np.uint8), ('lcsconf', np.uint8), ('lcachg', np.uint16))
+PRODUCT_DTYPES = dict(PRODUCTS)
+CHANGE_PRODUCTS = tuple(n for n, _ in PRODUCTS[:5])
+COVER_PRODUCTS = tuple(n for n, _ in PRODUCTS[5:])
+PRODUCT_BOT = 723546       # ccdgpu_product_params_default: bot, 1982-01-01
+PRODUCT_MAG_BANDS = 0x3E   # ... mag_bands, green .. swir2
+PRODUCT_MAX_CLASSES = 32   # labels[32]
 BANDS = ('blue', 'green', 'red', 'nir', 'swir1', 'swir2', 'thermal')
 PROCEDURES = ('standard_procedure', 'permanent_snow_procedure', 'insufficient_clear_procedure')
 
@@ -145,6 +154,25 @@ class Stats(ctypes.Structure):
                 ('cd_sweeps', ctypes.c_int64), ('flops', ctypes.c_int64), ('bytes', ctypes.c_int64),
                 ('detect_ms_device', _f64), ('pool_reruns', ctypes.c_int64), ('pool_cap', ctypes.c_int64),
                 ('wave_slots', ctypes.c_int64), ('n_cu', ctypes.c_int64)]
+
+
+class ProductParams(ctypes.Structure):
+    """ccdgpu_product_params (include/ccdgpu.h)."""
+    _fields_ = [('bot', ctypes.c_int64), ('mag_bands', _u32), ('cover', _i32), ('n_classes', _i32),
+                ('labels', ctypes.c_uint8 * PRODUCT_MAX_CLASSES), ('reserved0', _i32)]
+
+
+class Products(ctypes.Structure):
+    """struct ccdgpu_products: the ten output pointers, NULL for a product that is not wanted."""
+    _fields_ = [(name, ctypes.c_void_p) for name, _ in PRODUCTS]
+
+
+def default_product_params():
+    p = ProductParams()
+    p.bot, p.mag_bands, p.cover, p.n_classes = PRODUCT_BOT, PRODUCT_MAG_BANDS, COVER_EXTEND, 0
+    for k in range(PRODUCT_MAX_CLASSES):
+        p.labels[k] = k + 1
+    return p
 
 
 class Forest(ctypes.Structure):

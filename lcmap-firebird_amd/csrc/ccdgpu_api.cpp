@@ -81,6 +81,8 @@ struct Knobs {
     // CCDGPU_PREDICT_SLAB_PIXELS (test knob): pixels whose predicted values the device holds at a
     // time; 0: as many as keep a slab within PREDICT_SLAB_BYTES
     int predict_slab_pixels = 0;
+    // CCDGPU_PRODUCT_SLAB_PIXELS (test knob): the same for the product rasters (PRODUCT_SLAB_BYTES)
+    int product_slab_pixels = 0;
 };
 
 Knobs read_knobs() {
@@ -96,6 +98,7 @@ Knobs read_knobs() {
     if (const char *v = std::getenv("CCDGPU_KEEP_SLOTS")) k.keep_slots = std::atoi(v) != 0;
     if (const char *v = std::getenv("CCDGPU_POOL_PER_PIXEL")) k.pool_per_pixel = std::max(1, std::atoi(v));
     if (const char *v = std::getenv("CCDGPU_PREDICT_SLAB_PIXELS")) k.predict_slab_pixels = std::max(0, std::atoi(v));
+    if (const char *v = std::getenv("CCDGPU_PRODUCT_SLAB_PIXELS")) k.product_slab_pixels = std::max(0, std::atoi(v));
     return k;
 }
 
@@ -210,6 +213,7 @@ int ccdgpu_init_copy_cus(int device, int copy_cus, ccdgpu_ctx **out) {
     c->keep_slots = knobs.keep_slots;
     c->pool_per_pixel = knobs.pool_per_pixel;
     c->predict_slab_pixels = knobs.predict_slab_pixels;
+    c->product_slab_pixels = knobs.product_slab_pixels;
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) != hipSuccess) {
         delete c;

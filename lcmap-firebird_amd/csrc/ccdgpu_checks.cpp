@@ -1,8 +1,8 @@
 // ccdgpu_checks.cpp -- the part of the host API that touches no device: the error state, the
-// default parameters and the validators of parameters, shapes, transport-encoded batches, forests
-// and prediction requests.  The device code trusts what passes here, so this unit is kept free of
-// HIP and builds with a plain C++ compiler too (tests/native/host_checks.cpp runs it under
-// sanitizers).
+// default parameters and the validators of parameters, shapes, transport-encoded batches, forests,
+// prediction and product requests, with the product rule's year window.  The device code trusts
+// what passes here, so this unit is kept free of HIP and builds with a plain C++ compiler too
+// (tests/native/host_checks.cpp and product_checks.cpp run it under sanitizers).
 #include "ccdgpu_checks.h"
 
 #include <algorithm>
@@ -290,17 +290,42 @@ int forest_build(const ccdgpu_forest *f, int32_t cap, std::vector<unsigned char>
     return 0;
 }
 
-int predict_check_dates(int64_t n_dates, const int64_t *dates, double avg_days_yr) {
-    if (n_dates < 0) return fail(CCDGPU_EINVAL, "predict: n_dates must be >= 0, got " + std::to_string(n_dates));
-    if (n_dates > INT32_MAX) return fail(CCDGPU_EINVAL, "predict: n_dates must be < 2^31, got " + std::to_string(n_dates));
-    if (n_dates > 0 && !dates) return fail(CCDGPU_EINVAL, "predict: dates is NULL");
-    if (!std::isfinite(avg_days_yr) || !(avg_days_yr > 0.0))
-        return fail(CCDGPU_EINVAL, "predict: avg_days_yr must be finite and > 0, got " + std::to_string(avg_days_yr));
+// the date vector of a prediction or product request (`who`: "predict" / "products")
+static int check_dates(const std::string &who, int64_t n_dates, const int64_t *dates) {
+    if (n_dates < 0) return fail(CCDGPU_EINVAL, who + ": n_dates must be >= 0, got " + std::to_string(n_dates));
+    if (n_dates > INT32_MAX) return fail(CCDGPU_EINVAL, who + ": n_dates must be < 2^31, got " + std::to_string(n_dates));
+    if (n_dates > 0 && !dates) return fail(CCDGPU_EINVAL, who + ": dates is NULL");
     for (int64_t i = 0; i < n_dates; ++i)
         if (dates[i] < 1 || dates[i] > CCDGPU_PREDICT_MAX_DATE)
-            return fail(CCDGPU_EINVAL, "predict: dates[" + std::to_string(i) + "] = " + std::to_string(dates[i]) +
+            return fail(CCDGPU_EINVAL, who + ": dates[" + std::to_string(i) + "] = " + std::to_string(dates[i]) +
                                            " is outside 1 .. " + std::to_string(CCDGPU_PREDICT_MAX_DATE));
     return 0;
+}
+
+// the row table of a prediction or product request: counts, pointers, offsets
+static int check_table(const std::string &who, int64_t n_pix, const int64_t *row_offsets, int64_t n_rows, const ccdgpu_row *rows) {
+    if (n_pix < 0) return fail(CCDGPU_EINVAL, who + ": n_pix must be >= 0, got " + std::to_string(n_pix));
+    if (n_rows < 0) return fail(CCDGPU_EINVAL, who + ": n_rows must be >= 0, got " + std::to_string(n_rows));
+    if (!row_offsets) return fail(CCDGPU_EINVAL, who + ": row_offsets is NULL");
+    if (n_rows > 0 && !rows) return fail(CCDGPU_EINVAL, who + ": rows is NULL");
+    if (row_offsets[0] != 0)
+        return fail(CCDGPU_EINVAL, who + ": row_offsets[0] must be 0, got " + std::to_string(row_offsets[0]));
+    for (int64_t p = 0; p < n_pix; ++p)
+        if (row_offsets[p + 1] < row_offsets[p])
+            return fail(CCDGPU_EINVAL, who + ": row_offsets decrease at pixel " + std::to_string(p) + " (" +
+                                           std::to_string(row_offsets[p]) + " -> " + std::to_string(row_offsets[p + 1]) + ")");
+    if (row_offsets[n_pix] != n_rows)
+        return fail(CCDGPU_EINVAL, who + ": row_offsets[n_pix] is " + std::to_string(row_offsets[n_pix]) + ", n_rows is " +
+                                       std::to_string(n_rows));
+    return 0;
+}
+
+int predict_check_dates(int64_t n_dates, const int64_t *dates, double avg_days_yr) {
+    // (a bad count or pointer is named before avg_days_yr, a bad date after it)
+    if (n_dates < 0 || n_dates > INT32_MAX || (n_dates > 0 && !dates)) return check_dates("predict", n_dates, dates);
+    if (!std::isfinite(avg_days_yr) || !(avg_days_yr > 0.0))
+        return fail(CCDGPU_EINVAL, "predict: avg_days_yr must be finite and > 0, got " + std::to_string(avg_days_yr));
+    return check_dates("predict", n_dates, dates);
 }
 
 int predict_check_modes(int32_t cover, int32_t dtype) {
@@ -310,6 +335,51 @@ int predict_check_modes(int32_t cover, int32_t dtype) {
         return fail(CCDGPU_EINVAL, "predict: unknown dtype " + std::to_string(dtype));
     return 0;
 }
+
+// 1 January of proleptic-Gregorian year y as an ordinal (y >= 1)
+static int64_t year_start(int64_t y) {
+    const int64_t p = y - 1;
+    return p * 365 + p / 4 - p / 100 + p / 400 + 1;
+}
+
+void year_window(int64_t t, int64_t *a, int64_t *b) {
+    // the year of ordinal t: 400-, 100-, 4- and 1-year cycles of 146097, 36524, 1461 and 365 days
+    int64_t n = t - 1;
+    const int64_t n400 = n / 146097;
+    n %= 146097;
+    const int64_t n100 = n / 36524;
+    n %= 36524;
+    const int64_t n4 = n / 1461;
+    n %= 1461;
+    const int64_t n1 = n / 365;
+    int64_t y = n400 * 400 + n100 * 100 + n4 * 4 + n1 + 1;
+    if (n1 == 4 || n100 == 4) --y;  // 31 December of a leap year
+    *a = year_start(y);
+    *b = year_start(y + 1);
+}
+
+int products_check_params(const ccdgpu_product_params *p, const float *rfrawp, const struct ccdgpu_products *out) {
+    if (!p) return fail(CCDGPU_EINVAL, "products: params is NULL");
+    if (!out) return fail(CCDGPU_EINVAL, "products: out is NULL");
+    if (p->bot < 1 || p->bot > CCDGPU_PREDICT_MAX_DATE)
+        return fail(CCDGPU_EINVAL, "products: bot = " + std::to_string(p->bot) + " is outside 1 .. " +
+                                       std::to_string(CCDGPU_PREDICT_MAX_DATE));
+    if (p->mag_bands & ~0x7Fu) return fail(CCDGPU_EINVAL, "products: mag_bands must only use bits 0..6");
+    if (p->n_classes < 0 || p->n_classes > 32)
+        return fail(CCDGPU_EINVAL, "products: n_classes must be in [0, 32], got " + std::to_string(p->n_classes));
+    for (int32_t k = 0; k < p->n_classes; ++k)
+        if (p->labels[k] == 0) return fail(CCDGPU_EINVAL, "products: labels[" + std::to_string(k) + "] is 0 (labels are 1 .. 255)");
+    if (p->cover != CCDGPU_COVER_SPAN && p->cover != CCDGPU_COVER_EXTEND)
+        return fail(CCDGPU_EINVAL, "products: unknown cover " + std::to_string(p->cover));
+    const bool cover_out = out->lcpri || out->lcsec || out->lcpconf || out->lcsconf || out->lcachg;
+    if (cover_out && !rfrawp) return fail(CCDGPU_EINVAL, "products: a cover product is requested but rfrawp is NULL");
+    if (cover_out && p->n_classes == 0) return fail(CCDGPU_EINVAL, "products: a cover product is requested but n_classes is 0");
+    if (!cover_out && !out->sctime && !out->scmag && !out->sclast && !out->scstab && !out->scmqa)
+        return fail(CCDGPU_EINVAL, "products: no product is requested (all ten outputs are NULL)");
+    return 0;
+}
+
+int products_check_dates(int64_t n_dates, const int64_t *dates) { return check_dates("products", n_dates, dates); }
 
 }  // namespace ccdhost
 
@@ -380,22 +450,35 @@ int ccdgpu_forest_depth(const ccdgpu_forest *f, int32_t *max_depth) {
 
 int ccdgpu_predict_check(int64_t n_pix, const int64_t *row_offsets, int64_t n_rows, const ccdgpu_row *rows, int64_t n_dates,
                          const int64_t *dates, double avg_days_yr, int32_t cover, int32_t dtype) {
-    if (n_pix < 0) return fail(CCDGPU_EINVAL, "predict: n_pix must be >= 0, got " + std::to_string(n_pix));
-    if (n_rows < 0) return fail(CCDGPU_EINVAL, "predict: n_rows must be >= 0, got " + std::to_string(n_rows));
-    if (!row_offsets) return fail(CCDGPU_EINVAL, "predict: row_offsets is NULL");
-    if (n_rows > 0 && !rows) return fail(CCDGPU_EINVAL, "predict: rows is NULL");
-    if (row_offsets[0] != 0)
-        return fail(CCDGPU_EINVAL, "predict: row_offsets[0] must be 0, got " + std::to_string(row_offsets[0]));
-    for (int64_t p = 0; p < n_pix; ++p)
-        if (row_offsets[p + 1] < row_offsets[p])
-            return fail(CCDGPU_EINVAL, "predict: row_offsets decrease at pixel " + std::to_string(p) + " (" +
-                                           std::to_string(row_offsets[p]) + " -> " + std::to_string(row_offsets[p + 1]) + ")");
-    if (row_offsets[n_pix] != n_rows)
-        return fail(CCDGPU_EINVAL, "predict: row_offsets[n_pix] is " + std::to_string(row_offsets[n_pix]) + ", n_rows is " +
-                                       std::to_string(n_rows));
-    int rc = predict_check_dates(n_dates, dates, avg_days_yr);
-    if (rc) return rc;
+    int rc = check_table("predict", n_pix, row_offsets, n_rows, rows);
+    if (rc || (rc = predict_check_dates(n_dates, dates, avg_days_yr))) return rc;
     return predict_check_modes(cover, dtype);
+}
+
+void ccdgpu_product_params_default(ccdgpu_product_params *p) {
+    std::memset(p, 0, sizeof(*p));
+    p->bot = 723546;  // 1982-01-01
+    p->mag_bands = 0x3E;
+    p->cover = CCDGPU_COVER_EXTEND;
+    p->n_classes = 0;
+    for (int k = 0; k < 32; ++k) p->labels[k] = (uint8_t)(k + 1);
+}
+
+int ccdgpu_year_window(int64_t t, int64_t *a, int64_t *b) {
+    if (!a || !b) return fail(CCDGPU_EINVAL, "year_window: NULL argument");
+    if (t < 1 || t > CCDGPU_PREDICT_MAX_DATE)
+        return fail(CCDGPU_EINVAL, "year_window: t = " + std::to_string(t) + " is outside 1 .. " +
+                                       std::to_string(CCDGPU_PREDICT_MAX_DATE));
+    year_window(t, a, b);
+    return 0;
+}
+
+int ccdgpu_products_check(int64_t n_pix, const int64_t *row_offsets, int64_t n_rows, const ccdgpu_row *rows, const float *rfrawp,
+                          int64_t n_dates, const int64_t *dates, const ccdgpu_product_params *params,
+                          const struct ccdgpu_products *out) {
+    int rc = check_table("products", n_pix, row_offsets, n_rows, rows);
+    if (rc || (rc = products_check_dates(n_dates, dates))) return rc;
+    return products_check_params(params, rfrawp, out);
 }
 
 }  // extern "C"

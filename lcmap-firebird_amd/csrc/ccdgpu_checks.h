@@ -49,4 +49,10 @@ int forest_build(const ccdgpu_forest *f, int32_t cap, std::vector<unsigned char>
 int predict_check_dates(int64_t n_dates, const int64_t *dates, double avg_days_yr);
 int predict_check_modes(int32_t cover, int32_t dtype);
 
+// a(t), b(t) of the product rule (include/ccdgpu.h) for a checked date t
+void year_window(int64_t t, int64_t *a, int64_t *b);
+// the parts of ccdgpu_products_check the chained path shares: the date vector; the parameters and outputs
+int products_check_dates(int64_t n_dates, const int64_t *dates);
+int products_check_params(const ccdgpu_product_params *p, const float *rfrawp, const struct ccdgpu_products *out);
+
 }  // namespace ccdhost

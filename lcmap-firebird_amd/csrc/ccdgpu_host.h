@@ -1,9 +1,10 @@
 // ccdgpu_host.h -- what the host API's units share (ccdgpu_api.cpp: contexts, staging, detection,
-// row chain and fetches; ccdgpu_forest.cpp; ccdgpu_predict.cpp): the owners of device memory,
+// row chain and fetches; ccdgpu_forest.cpp; ccdgpu_predict.cpp; ccdgpu_products.cpp): the owners of device memory,
 // pinned memory and events, and the context.  Private to csrc/.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "ccd_products.h"
 #include "ccdgpu_checks.h"
 
 #define HIPCHK(expr)                                                                       \
@@ -200,6 +201,18 @@ struct ccdgpu_ctx {
     DevBuf<unsigned char> p_out;
     DevBuf<int32_t> p_idx;
     Event p_ev[2];
+    // product rasters (ccd_products.hip): pixels whose output the device holds at a time
+    // (CCDGPU_PRODUCT_SLAB_PIXELS, test knob; 0: as many as keep a slab within PRODUCT_SLAB_BYTES) and
+    // the scratch of a slab -- dates with their year windows (and the host copy they are uploaded
+    // from), offsets, table rows, rfrawp rows, records, product planes
+    int64_t product_slab_pixels = 0;
+    std::vector<int64_t> q_win_host;
+    DevBuf<int64_t> q_win, q_off;
+    DevBuf<ccdgpu_row> q_rows;
+    DevBuf<float> q_rf;
+    DevBuf<CcdProductRecord> q_rec;
+    DevBuf<unsigned char> q_out;
+    Event q_ev[2];
     // Buffers and events free themselves (after this body, so after the streams are gone:
     // ccdgpu_destroy has synchronised every stream); here only what has an order or a condition.
     ~ccdgpu_ctx();
