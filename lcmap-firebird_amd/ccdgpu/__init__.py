@@ -32,146 +32,12 @@ class QAValueError(ValueError):
     """Unsupported bit-packed QA value: the analogue of pyccd qa.qabitval's ValueError."""
 
 
+EXPORTS = tuple(abi.SIGNATURES)
+
+
 def _declare(L):
-    c = ctypes
-    L.ccdgpu_version.restype = c.c_char_p
-    L.ccdgpu_last_error.restype = c.c_char_p
-    L.ccdgpu_params_default.argtypes = [c.POINTER(abi.Params)]
-    L.ccdgpu_init.argtypes = [c.c_int, c.POINTER(c.c_void_p)]
-    if hasattr(L, 'ccdgpu_fetch_batch_rows_into'):
-        L.ccdgpu_fetch_batch_rows_into.argtypes = [c.c_void_p, c.c_void_p, c.c_void_p, c.c_int32, c.c_void_p, c.c_int64,
-                                                   c.c_void_p, c.c_int64, c.c_void_p, c.c_int64, c.POINTER(c.c_int64)]
-        L.ccdgpu_fetch_batch_rows_into.restype = c.c_int
-    if hasattr(L, 'ccdgpu_run_slot_begin'):
-        L.ccdgpu_run_slot_begin.argtypes = [c.c_void_p, c.c_int32]
-        L.ccdgpu_run_slot_begin.restype = c.c_int
-        L.ccdgpu_run_query.argtypes = [c.c_void_p]
-        L.ccdgpu_run_query.restype = c.c_int
-        L.ccdgpu_run_slot_end.argtypes = [c.c_void_p, c.POINTER(c.c_double)]
-        L.ccdgpu_run_slot_end.restype = c.c_int
-    if hasattr(L, 'ccdgpu_run_slot_begin_rows'):
-        L.ccdgpu_run_slot_begin_rows.argtypes = [c.c_void_p, c.c_int32, c.c_void_p, c.c_void_p, c.c_int32, c.c_void_p,
-                                                 c.c_int64, c.c_void_p, c.c_int64, c.c_void_p, c.c_int64]
-        L.ccdgpu_run_slot_begin_rows.restype = c.c_int
-        L.ccdgpu_run_slot_end_rows.argtypes = [c.c_void_p, c.POINTER(c.c_double), c.POINTER(c.c_int64)]
-        L.ccdgpu_run_slot_end_rows.restype = c.c_int
-    if hasattr(L, 'ccdgpu_init_copy_cus'):
-        L.ccdgpu_init_copy_cus.argtypes = [c.c_int, c.c_int, c.POINTER(c.c_void_p)]
-        L.ccdgpu_init_copy_cus.restype = c.c_int
-    L.ccdgpu_destroy.argtypes = [c.c_void_p]
-    L.ccdgpu_device_count.argtypes = [c.POINTER(c.c_int)]
-    if hasattr(L, 'ccdgpu_encode_chips'):  # (absent from libraries built before it: A/B runs)
-        L.ccdgpu_encoded_bound.argtypes = [c.c_int32, c.c_void_p, c.c_void_p]
-        L.ccdgpu_encoded_bound.restype = c.c_int64
-        L.ccdgpu_encode_chips.argtypes = [c.c_int32, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p,
-                                          c.c_int64, c.c_int32, c.c_uint16, c.c_uint16]
-        L.ccdgpu_encode_chips.restype = c.c_int64
-        L.ccdgpu_encode_vector_path.restype = c.c_int32
-        L.ccdgpu_stage_slot_encoded.argtypes = [c.c_void_p, c.c_int32, c.c_void_p, c.c_int32, c.c_void_p, c.c_void_p,
-                                                c.c_void_p, c.c_void_p, c.c_int64]
-        L.ccdgpu_stage_slot_encoded.restype = c.c_int
-    if hasattr(L, 'ccdgpu_encode_chips_flags'):  # (the bit-packed mode 2: pack=True needs it)
-        L.ccdgpu_encoded_bound_flags.argtypes = [c.c_int32, c.c_void_p, c.c_void_p, c.c_uint32]
-        L.ccdgpu_encoded_bound_flags.restype = c.c_int64
-        L.ccdgpu_encode_chips_flags.argtypes = [c.c_int32, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p,
-                                                c.c_int64, c.c_int32, c.c_uint16, c.c_uint16, c.c_uint32]
-        L.ccdgpu_encode_chips_flags.restype = c.c_int64
-    if hasattr(L, 'ccdgpu_encoded_check'):
-        L.ccdgpu_encoded_check.argtypes = [c.c_int32, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64]
-        L.ccdgpu_encoded_check.restype = c.c_int
-    if hasattr(L, 'ccdgpu_device_numa_node'):  # (absent from libraries built before it: A/B runs)
-        L.ccdgpu_device_numa_node.argtypes = [c.c_int, c.POINTER(c.c_int)]
-        L.ccdgpu_device_numa_node.restype = c.c_int
-    L.ccdgpu_synchronize.argtypes = [c.c_void_p]
-    L.ccdgpu_forest_check.argtypes = [c.POINTER(abi.Forest)]
-    L.ccdgpu_forest_check.restype = c.c_int
-    L.ccdgpu_forest_depth.argtypes = [c.POINTER(abi.Forest), c.POINTER(c.c_int32)]
-    L.ccdgpu_forest_depth.restype = c.c_int
-    L.ccdgpu_forest_set.argtypes = [c.c_void_p, c.POINTER(abi.Forest)]
-    L.ccdgpu_forest_set.restype = c.c_int
-    L.ccdgpu_forest_clear.argtypes = [c.c_void_p]
-    L.ccdgpu_forest_clear.restype = c.c_int
-    L.ccdgpu_classify.argtypes = [c.c_void_p, c.c_void_p, c.c_int64, c.c_void_p, c.POINTER(c.c_double)]
-    L.ccdgpu_classify.restype = c.c_int
-    L.ccdgpu_classify_rows.argtypes = [c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64, c.POINTER(c.c_int64),
-                                       c.POINTER(c.c_double)]
-    L.ccdgpu_classify_rows.restype = c.c_int
-    L.ccdgpu_predict_check.argtypes = [c.c_int64, c.c_void_p, c.c_int64, c.c_void_p, c.c_int64, c.c_void_p, c.c_double,
-                                       c.c_int32, c.c_int32]
-    L.ccdgpu_predict_check.restype = c.c_int
-    L.ccdgpu_predict.argtypes = [c.c_void_p, c.c_int64, c.c_void_p, c.c_void_p, c.c_int64, c.c_void_p, c.c_double,
-                                 c.c_int32, c.c_int32, c.c_void_p, c.c_void_p, c.POINTER(c.c_double)]
-    L.ccdgpu_predict.restype = c.c_int
-    L.ccdgpu_predict_rows.argtypes = [c.c_void_p, c.c_int32, c.c_int64, c.c_void_p, c.c_double, c.c_int32, c.c_int32,
-                                      c.c_void_p, c.c_void_p, c.POINTER(c.c_double)]
-    L.ccdgpu_predict_rows.restype = c.c_int
-    L.ccdgpu_coefficient_matrix.argtypes = [c.c_void_p, c.c_int64, c.c_void_p, c.c_double, c.c_void_p]
-    L.ccdgpu_coefficient_matrix.restype = c.c_int
-    L.ccdgpu_product_params_default.argtypes = [c.POINTER(abi.ProductParams)]
-    L.ccdgpu_product_params_default.restype = None
-    L.ccdgpu_year_window.argtypes = [c.c_int64, c.POINTER(c.c_int64), c.POINTER(c.c_int64)]
-    L.ccdgpu_year_window.restype = c.c_int
-    L.ccdgpu_products_check.argtypes = [c.c_int64, c.c_void_p, c.c_int64, c.c_void_p, c.c_void_p, c.c_int64, c.c_void_p,
-                                        c.POINTER(abi.ProductParams), c.POINTER(abi.Products)]
-    L.ccdgpu_products_check.restype = c.c_int
-    L.ccdgpu_products.argtypes = [c.c_void_p, c.c_int64, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64, c.c_void_p,
-                                  c.POINTER(abi.ProductParams), c.POINTER(abi.Products), c.POINTER(c.c_double)]
-    L.ccdgpu_products.restype = c.c_int
-    L.ccdgpu_products_rows.argtypes = [c.c_void_p, c.c_int32, c.c_void_p, c.c_int64, c.c_void_p, c.POINTER(abi.ProductParams),
-                                       c.POINTER(abi.Products), c.POINTER(c.c_double)]
-    L.ccdgpu_products_rows.restype = c.c_int
-    L.ccdgpu_chip_row_count.argtypes = [c.c_void_p, c.c_int32, c.POINTER(c.c_int64)]
-    L.ccdgpu_chip_row_count.restype = c.c_int
-    L.ccdgpu_detect_batch.argtypes = [c.c_void_p, c.POINTER(abi.Params), c.c_int32, c.c_int32,
-                                      c.c_void_p, c.c_void_p, c.c_void_p, c.POINTER(abi.Result)]
-    L.ccdgpu_result_free.argtypes = [c.POINTER(abi.Result)]
-    L.ccdgpu_stage.argtypes = [c.c_void_p, c.POINTER(abi.Params), c.c_int32, c.c_int32, c.c_int32,
-                               c.c_void_p, c.c_void_p, c.c_void_p]
-    L.ccdgpu_stage_chips.argtypes = [c.c_void_p, c.POINTER(abi.Params), c.c_int32, c.c_void_p, c.c_void_p,
-                                     c.c_void_p, c.c_void_p, c.c_void_p]
-    L.ccdgpu_stage_slot_chips.argtypes = [c.c_void_p, c.c_int32, c.POINTER(abi.Params), c.c_int32, c.c_void_p,
-                                          c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p]
-    L.ccdgpu_fetch_batch_rows.argtypes = [c.c_void_p, c.c_void_p, c.c_void_p, c.c_int32, c.POINTER(abi.Rows)]
-    L.ccdgpu_stage_chipmunk.argtypes = [c.c_void_p, c.POINTER(abi.Params), c.c_int32, c.c_int32, c.c_int32,
-                                        c.c_void_p, c.c_char_p, c.c_int64, c.c_void_p,
-                                        c.POINTER(c.c_double)]
-    L.ccdgpu_staged_inputs.argtypes = [c.c_void_p, c.c_void_p, c.c_void_p]
-    L.ccdgpu_host_alloc.argtypes = [c.c_size_t, c.POINTER(c.c_void_p)]
-    L.ccdgpu_host_free.argtypes = [c.c_void_p]
-    L.ccdgpu_stage_slot.argtypes = [c.c_void_p, c.c_int32, c.POINTER(abi.Params), c.c_int32, c.c_int32, c.c_int32,
-                                    c.c_void_p, c.c_void_p, c.c_void_p]
-    L.ccdgpu_run_slot.argtypes = [c.c_void_p, c.c_int32, c.POINTER(c.c_double)]
-    L.ccdgpu_fetch_rows.argtypes = [c.c_void_p, c.c_int32, c.c_int32, c.c_int32, c.c_int32, c.POINTER(abi.Rows)]
-    L.ccdgpu_rows_free.argtypes = [c.POINTER(abi.Rows)]
-    L.ccdgpu_run_staged.argtypes = [c.c_void_p, c.POINTER(c.c_double)]
-    L.ccdgpu_fetch_staged.argtypes = [c.c_void_p, c.c_int32, c.POINTER(abi.Result)]
-    L.ccdgpu_last_stats.argtypes = [c.c_void_p, c.POINTER(abi.Stats)]
-    L.ccdgpu_diag_counters.argtypes = [c.c_void_p, c.POINTER(c.c_uint64), c.c_int32]
-    for name in ('ccdgpu_init', 'ccdgpu_destroy', 'ccdgpu_device_count', 'ccdgpu_synchronize',
-                 'ccdgpu_detect_batch', 'ccdgpu_stage', 'ccdgpu_stage_chips', 'ccdgpu_stage_slot_chips',
-                 'ccdgpu_fetch_batch_rows', 'ccdgpu_stage_chipmunk', 'ccdgpu_staged_inputs',
-                 'ccdgpu_run_staged', 'ccdgpu_fetch_staged', 'ccdgpu_fetch_rows', 'ccdgpu_host_alloc',
-                 'ccdgpu_host_free', 'ccdgpu_stage_slot', 'ccdgpu_run_slot', 'ccdgpu_rows_free', 'ccdgpu_fetch_rows',
-                 'ccdgpu_last_stats', 'ccdgpu_diag_counters'):
-        getattr(L, name).restype = c.c_int
-    return L
-
-
-EXPORTS = ('ccdgpu_version', 'ccdgpu_last_error', 'ccdgpu_params_default', 'ccdgpu_init',
-           'ccdgpu_destroy', 'ccdgpu_device_count', 'ccdgpu_synchronize', 'ccdgpu_detect_batch',
-           'ccdgpu_result_free', 'ccdgpu_stage', 'ccdgpu_stage_chipmunk', 'ccdgpu_staged_inputs',
-           'ccdgpu_run_staged', 'ccdgpu_fetch_staged', 'ccdgpu_fetch_rows', 'ccdgpu_rows_free',
-           'ccdgpu_host_alloc', 'ccdgpu_host_free', 'ccdgpu_stage_slot', 'ccdgpu_run_slot',
-           'ccdgpu_last_stats', 'ccdgpu_diag_counters', 'ccdgpu_stage_chips', 'ccdgpu_stage_slot_chips',
-           'ccdgpu_fetch_batch_rows', 'ccdgpu_device_numa_node', 'ccdgpu_encoded_bound', 'ccdgpu_encode_chips',
-           'ccdgpu_encode_vector_path', 'ccdgpu_stage_slot_encoded', 'ccdgpu_init_copy_cus',
-           'ccdgpu_run_slot_begin', 'ccdgpu_run_query', 'ccdgpu_run_slot_end', 'ccdgpu_fetch_batch_rows_into',
-           'ccdgpu_run_slot_begin_rows', 'ccdgpu_run_slot_end_rows', 'ccdgpu_encoded_check',
-           'ccdgpu_forest_check', 'ccdgpu_forest_depth', 'ccdgpu_forest_set', 'ccdgpu_forest_clear',
-           'ccdgpu_classify', 'ccdgpu_classify_rows', 'ccdgpu_encoded_bound_flags', 'ccdgpu_encode_chips_flags',
-           'ccdgpu_predict_check', 'ccdgpu_predict', 'ccdgpu_predict_rows', 'ccdgpu_coefficient_matrix',
-           'ccdgpu_product_params_default', 'ccdgpu_year_window', 'ccdgpu_products_check', 'ccdgpu_products',
-           'ccdgpu_products_rows', 'ccdgpu_chip_row_count')
+    """The signatures of abi.SIGNATURES on library ``L``; a symbol it lacks is left for ctypes to name."""
+    return abi.declare(L, abi.SIGNATURES)
 
 
 def lib():
@@ -194,6 +60,44 @@ def _check(rc):
         raise QAValueError(last_error())
     if rc != 0:
         raise CcdGpuError(rc, last_error())
+
+
+def _params(params):
+    """abi.Params: ``params`` itself, or made from a pyccd-style dict (None: the defaults)."""
+    return params if isinstance(params, abi.Params) else abi.params_from_dict(params)
+
+
+def _timed(fn, *args, after=()):
+    """(return code, kernel seconds) of a library call whose ``double *kernel_seconds`` follows ``args``."""
+    secs = ctypes.c_double(0.0)
+    return fn(*(args + (ctypes.byref(secs),) + tuple(after))), secs.value
+
+
+def _take(rc, out, ok=(0,)):
+    """The numpy copy of a library-owned abi.Result / abi.Rows the call that returned ``rc`` filled
+    (raising unless rc is in ``ok``); the library's memory is freed either way."""
+    L = lib()
+    unpack, free = (abi.unpack, L.ccdgpu_result_free) if isinstance(out, abi.Result) else (abi.unpack_rows, L.ccdgpu_rows_free)
+    try:
+        if rc not in ok:
+            _check(rc)
+        return unpack(out)
+    finally:
+        free(ctypes.byref(out))
+
+
+def _allocator(pinned):
+    """``alloc(shape, dtype)``: page-locked arrays (pinned_empty) or numpy's own."""
+    return pinned_empty if pinned else np.empty
+
+
+def _chip_coords(cx, cy, n_chips):
+    """cx / cy as int32 arrays of one entry per chip."""
+    cx = np.ascontiguousarray(cx, dtype=np.int32)
+    cy = np.ascontiguousarray(cy, dtype=np.int32)
+    if cx.shape != (n_chips,) or cy.shape != (n_chips,):
+        raise ValueError('cx / cy need one entry per chip (%d)' % n_chips)
+    return cx, cy
 
 
 def version():
@@ -232,13 +136,7 @@ class ChipBatch(object):
         """``storage``: (dates int64, spectra int16, qa uint16) 1-D arrays of at least the batch's
         sizes (e.g. ``batch_storage``, reused across batches): the batch's arrays are their
         prefixes instead of new allocations."""
-        self.n_pix = np.ascontiguousarray(n_pix, dtype=np.int32).reshape(-1)
-        self.n_obs = np.ascontiguousarray(n_obs, dtype=np.int32).reshape(-1)
-        if self.n_pix.shape != self.n_obs.shape or self.n_pix.size == 0:
-            raise ValueError('n_pix and n_obs must be equal-length, non-empty')
-        self.obs_off = np.concatenate([[0], np.cumsum(self.n_obs, dtype=np.int64)])
-        self.pix_off = np.concatenate([[0], np.cumsum(self.n_pix, dtype=np.int64)])
-        self.data_off = np.concatenate([[0], np.cumsum(self.n_pix.astype(np.int64) * self.n_obs)])
+        self._init_shape(n_pix, n_obs)
         nd, ns = int(self.obs_off[-1]), int(self.data_off[-1])
         self.storage = storage
         if storage is not None:
@@ -248,10 +146,20 @@ class ChipBatch(object):
                 raise ValueError('storage too small or of the wrong types for this batch')
             self.dates, self.spectra, self.qa = sd[:nd], ss[:7 * ns], sq[:ns]
             return
-        alloc = pinned_empty if pinned else np.empty
+        alloc = _allocator(pinned)
         self.dates = alloc((nd,), np.int64)
         self.spectra = alloc((7 * ns,), np.int16)
         self.qa = alloc((ns,), np.uint16)
+
+    def _init_shape(self, n_pix, n_obs):
+        """The chips' pixel / observation counts and the offsets of their dates, pixels and data."""
+        self.n_pix = np.ascontiguousarray(n_pix, dtype=np.int32).reshape(-1)
+        self.n_obs = np.ascontiguousarray(n_obs, dtype=np.int32).reshape(-1)
+        if self.n_pix.shape != self.n_obs.shape or self.n_pix.size == 0:
+            raise ValueError('n_pix and n_obs must be equal-length, non-empty')
+        self.obs_off = np.concatenate([[0], np.cumsum(self.n_obs, dtype=np.int64)])
+        self.pix_off = np.concatenate([[0], np.cumsum(self.n_pix, dtype=np.int64)])
+        self.data_off = np.concatenate([[0], np.cumsum(self.n_pix.astype(np.int64) * self.n_obs)])
 
     @property
     def n_chips(self):
@@ -311,13 +219,7 @@ class EncodedBatch(ChipBatch):
     """
 
     def __init__(self, n_pix, n_obs, storage=None, pinned=True, pack=False):
-        self.n_pix = np.ascontiguousarray(n_pix, dtype=np.int32).reshape(-1)
-        self.n_obs = np.ascontiguousarray(n_obs, dtype=np.int32).reshape(-1)
-        if self.n_pix.shape != self.n_obs.shape or self.n_pix.size == 0:
-            raise ValueError('n_pix and n_obs must be equal-length, non-empty')
-        self.obs_off = np.concatenate([[0], np.cumsum(self.n_obs, dtype=np.int64)])
-        self.pix_off = np.concatenate([[0], np.cumsum(self.n_pix, dtype=np.int64)])
-        self.data_off = np.concatenate([[0], np.cumsum(self.n_pix.astype(np.int64) * self.n_obs)])
+        self._init_shape(n_pix, n_obs)
         self.pack = bool(pack)
         bound = _encoded_bound(self.n_chips, self.n_pix, self.n_obs, self.pack)
         nd = int(self.obs_off[-1])
@@ -328,7 +230,7 @@ class EncodedBatch(ChipBatch):
                 raise ValueError('storage too small or of the wrong types for this batch')
             self.dates, self.buf = sd[:nd], sb
         else:
-            alloc = pinned_empty if pinned else np.empty
+            alloc = _allocator(pinned)
             self.dates, self.buf = alloc((nd,), np.int64), alloc((bound,), np.uint8)
         self.spectra = self.qa = None
         self.bound = bound
@@ -417,7 +319,7 @@ def encode_storage(max_chips, max_pix, max_obs, pinned=True, pack=False):
     np_ = np.full(n, int(max_pix), dtype=np.int32)
     no = np.full(n, int(max_obs), dtype=np.int32)
     bound = _encoded_bound(n, np_, no, pack)
-    alloc = pinned_empty if pinned else np.empty
+    alloc = _allocator(pinned)
     return alloc((n * int(max_obs),), np.int64), alloc((bound,), np.uint8)
 
 
@@ -427,7 +329,7 @@ def unread_drop_bits(params=None):
     classes them as fill / cloud / shadow whatever else is set, and no procedure keeps those
     classes); fill observations stay strict (their bands must be -9999).  For non-bit-packed QA
     (class values, not bits) only the lossless (fill bit 0) setting applies."""
-    p = params if isinstance(params, abi.Params) else abi.params_from_dict(params)
+    p = _params(params)
     if not p.qa_bitpacked:
         return 0, 0
     bits = [int(p.qa_fill), int(p.qa_cloud), int(p.qa_shadow)]
@@ -487,9 +389,26 @@ def _predict_buffers(out, seg_index, n_pix, n_dates, dtype):
     return out, (np.empty((n_pix, n_dates), dtype=np.int32) if seg_index else None)
 
 
-def predict_check(row_offsets, rows, dates, avg_days_yr=365.2425, cover=0, dtype=0, n_pix=None, n_rows=None):
-    """ccdgpu_predict_check (no device needed) over array-likes; None passes a NULL pointer, n_pix
-    / n_rows default to the arrays' sizes.  Raises ValueError with the library's message."""
+def _ptr(a):
+    return None if a is None else a.ctypes.data
+
+
+def _row_table(row_offsets, rows):
+    """(row_offsets int64 [n_pix + 1], rows abi.ROW_DTYPE) of a host table of segment rows, checked
+    against each other."""
+    off = np.ascontiguousarray(row_offsets, dtype=np.int64).reshape(-1)
+    r = np.ascontiguousarray(rows, dtype=abi.ROW_DTYPE).reshape(-1)
+    if off.shape[0] < 1:
+        raise ValueError('row_offsets must have n_pix + 1 entries')
+    if int(off[-1]) != r.shape[0]:
+        raise ValueError('row_offsets end at %d, the table has %d rows' % (int(off[-1]), r.shape[0]))
+    return off, r
+
+
+def _check_args(row_offsets, rows, dates, n_pix, n_rows):
+    """The table and date arguments of ccdgpu_predict_check / ccdgpu_products_check from array-likes
+    that may be None (a NULL pointer): ((n_pix, row_offsets, n_rows, rows), (n_dates, dates), the
+    arrays the pointers point into).  n_pix / n_rows default to the arrays' sizes."""
     off = None if row_offsets is None else np.ascontiguousarray(row_offsets, dtype=np.int64).reshape(-1)
     r = None if rows is None else np.ascontiguousarray(rows, dtype=abi.ROW_DTYPE).reshape(-1)
     d = None if dates is None else _predict_dates(dates)
@@ -497,14 +416,17 @@ def predict_check(row_offsets, rows, dates, avg_days_yr=365.2425, cover=0, dtype
         n_pix = 0 if off is None else off.shape[0] - 1
     if n_rows is None:
         n_rows = 0 if r is None else r.shape[0]
-    n_dates = 0 if d is None else d.shape[0]
-    if dates is None:
-        n_dates = 1  # (a NULL date vector of no dates is fine: ask for one)
+    n_dates = 1 if d is None else d.shape[0]  # (a NULL date vector of no dates is fine: ask for one)
     if off is not None and off.shape[0] < n_pix + 1:
         raise ValueError('row_offsets has %d entries, n_pix + 1 is %d' % (off.shape[0], n_pix + 1))
-    ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
-    if lib().ccdgpu_predict_check(int(n_pix), ptr(off), int(n_rows), ptr(r), int(n_dates), ptr(d), float(avg_days_yr),
-                                  int(cover), int(dtype)) != 0:
+    return (int(n_pix), _ptr(off), int(n_rows), _ptr(r)), (int(n_dates), _ptr(d)), (off, r, d)
+
+
+def predict_check(row_offsets, rows, dates, avg_days_yr=365.2425, cover=0, dtype=0, n_pix=None, n_rows=None):
+    """ccdgpu_predict_check (no device needed) over array-likes; None passes a NULL pointer, n_pix
+    / n_rows default to the arrays' sizes.  Raises ValueError with the library's message."""
+    table, when, keep = _check_args(row_offsets, rows, dates, n_pix, n_rows)  # (keep: alive over the call)
+    if lib().ccdgpu_predict_check(*(table + when + (float(avg_days_yr), int(cover), int(dtype)))) != 0:
         raise ValueError(last_error())
 
 
@@ -591,25 +513,54 @@ def products_check(row_offsets, rows, dates, rfrawp=None, params=None, want=abi.
     ``params`` the defaults), n_pix / n_rows default to the arrays' sizes; ``want`` names the outputs
     that are requested (as non-NULL pointers that are not written).  Raises ValueError with the
     library's message."""
-    off = None if row_offsets is None else np.ascontiguousarray(row_offsets, dtype=np.int64).reshape(-1)
-    r = None if rows is None else np.ascontiguousarray(rows, dtype=abi.ROW_DTYPE).reshape(-1)
-    d = None if dates is None else _predict_dates(dates)
+    table, when, keep = _check_args(row_offsets, rows, dates, n_pix, n_rows)  # (keep: alive over the call)
     rf = None if rfrawp is None else np.ascontiguousarray(rfrawp, dtype=np.float32)
-    if n_pix is None:
-        n_pix = 0 if off is None else off.shape[0] - 1
-    if n_rows is None:
-        n_rows = 0 if r is None else r.shape[0]
-    n_dates = 1 if d is None else d.shape[0]  # (a NULL date vector of no dates is fine: ask for one)
-    if off is not None and off.shape[0] < n_pix + 1:
-        raise ValueError('row_offsets has %d entries, n_pix + 1 is %d' % (off.shape[0], n_pix + 1))
     p = product_params() if params is None else params
     ptrs = abi.Products()
     for name in want:
         setattr(ptrs, name, 1)
-    ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
-    if lib().ccdgpu_products_check(int(n_pix), ptr(off), int(n_rows), ptr(r), ptr(rf), int(n_dates), ptr(d),
-                                   None if params is False else ctypes.byref(p), ctypes.byref(ptrs)) != 0:
+    if lib().ccdgpu_products_check(*(table + (_ptr(rf),) + when + (None if params is False else ctypes.byref(p),
+                                                                     ctypes.byref(ptrs)))) != 0:
         raise ValueError(last_error())
+
+
+class _Staged(object):
+    """The shape of a staged batch, one record for every staging form: the host arrays to keep
+    alive, the chips' pixel and observation counts, and whether the batch is a ChipBatch (an
+    EncodedBatch too) rather than uniform arrays.  ``_Staged()`` is "nothing staged"."""
+
+    def __init__(self, keep=None, n_pix=(), n_obs=(), is_batch=False):
+        self.keep = keep
+        self.n_pix = np.asarray(n_pix, dtype=np.int32).reshape(-1)
+        self.n_obs = np.asarray(n_obs, dtype=np.int32).reshape(-1)
+        self.is_batch = is_batch
+
+    @classmethod
+    def uniform(cls, keep, n_chips, n_pix, n_obs):
+        """``n_chips`` chips of (n_pix, n_obs) each: stage / stage_slot / stage_chipmunk / detect_batch."""
+        return cls(keep, [n_pix] * n_chips, [n_obs] * n_chips)
+
+    @classmethod
+    def of_batch(cls, batch):
+        return cls(batch, batch.n_pix, batch.n_obs, True)
+
+    @property
+    def n_chips(self):
+        return int(self.n_pix.size)
+
+    @property
+    def total_pixels(self):
+        """Pixels of the whole batch; None with nothing staged."""
+        return None if self.keep is None else int(self.n_pix.sum(dtype=np.int64))
+
+    @property
+    def mask_words(self):
+        """uint32 words per pixel of a batch row fetch's mask: set by the chip with most observations."""
+        return (int(self.n_obs.max()) + 31) // 32
+
+    def chip_pixels(self, chip):
+        """Pixels of chip ``chip``; None for no such chip, or with nothing staged."""
+        return int(self.n_pix[chip]) if 0 <= chip < self.n_chips else None
 
 
 class Context(object):
@@ -620,12 +571,34 @@ class Context(object):
         blits), the rest for detection (ccdgpu_init_copy_cus, include/ccdgpu.h)."""
         self.qa_error = False
         self._ctx = ctypes.c_void_p()
-        L = lib()
-        if copy_cus and hasattr(L, 'ccdgpu_init_copy_cus'):
-            _check(L.ccdgpu_init_copy_cus(int(device), int(copy_cus), ctypes.byref(self._ctx)))
+        self._last = _Staged()     # the batch of the last run (of stage / stage_chips: as soon as staged)
+        self._slots = {}           # input slot -> _Staged of the batch uploaded into it
+        self._pending_slot = None  # slot of a run_slot_begin* without its run_slot_end* yet
+        self._rows_req = None      # (cx, cy, bufs, width, n_pix, words, cap) of a run_slot_begin_rows
+        self._forest_shape = None  # (n_features, n_classes) of the forest set
+        self.forest_seconds = self.predict_seconds = self.products_seconds = 0.0
+        self.forest_rows = 0
+        if copy_cus:
+            _check(lib().ccdgpu_init_copy_cus(int(device), int(copy_cus), ctypes.byref(self._ctx)))
         else:
-            _check(L.ccdgpu_init(int(device), ctypes.byref(self._ctx)))
+            _check(lib().ccdgpu_init(int(device), ctypes.byref(self._ctx)))
         self.device = device
+
+    def _finish(self, rc):
+        """End of a run: raise on failure; an unsupported QA value leaves results (the pixel's
+        procedure is -1 in fetch) and sets ``qa_error``."""
+        if rc not in (0, abi.E_QA):
+            _check(rc)
+        self.qa_error = rc == abi.E_QA
+
+    def _chip_pixels(self, chip, probe, message):
+        """Pixels of chip ``chip`` of the last run.  Nothing staged here, or no such chip: ``probe()`` -- the
+        library call without buffers -- raises with the library's reason, or else ``message`` is raised."""
+        n_pix = self._last.chip_pixels(chip)
+        if n_pix is None:
+            probe()
+            raise CcdGpuError(abi.E_INVAL, message)
+        return n_pix
 
     def close(self):
         if self._ctx:
@@ -648,18 +621,13 @@ class Context(object):
         n_pix, n_obs = qa.shape
         if spectra.shape != (7, n_pix, n_obs) or dates.shape != (n_obs,):
             raise ValueError('shape mismatch: dates %s spectra %s qa %s' % (dates.shape, spectra.shape, qa.shape))
-        p = params if isinstance(params, abi.Params) else abi.params_from_dict(params)
+        p = _params(params)
         res = abi.Result()
         rc = lib().ccdgpu_detect_batch(self._ctx, ctypes.byref(p), n_pix, n_obs, dates.ctypes.data,
                                        spectra.ctypes.data, qa.ctypes.data, ctypes.byref(res))
         if rc in (0, abi.E_QA):  # the context's last run is now this one-chip batch (predict_rows sizes its output by it)
-            self._keep, self._n_pix = (dates, spectra, qa), n_pix
-        try:
-            if rc not in (0, abi.E_QA):
-                _check(rc)
-            u = abi.unpack(res)
-        finally:
-            lib().ccdgpu_result_free(ctypes.byref(res))
+            self._last = _Staged.uniform((dates, spectra, qa), 1, n_pix, n_obs)
+        u = _take(rc, res, ok=(0, abi.E_QA))
         if rc == abi.E_QA:
             err = QAValueError(last_error())
             err.result = u
@@ -671,23 +639,21 @@ class Context(object):
         """dates [C][n], spectra [C][7][n_pix][n], qa [C][n_pix][n] -> staged on the device."""
         dates, spectra, qa = _as_inputs(dates, spectra, qa)
         n_chips, n_pix, n_obs = qa.shape
-        p = params if isinstance(params, abi.Params) else abi.params_from_dict(params)
+        p = _params(params)
         _check(lib().ccdgpu_stage(self._ctx, ctypes.byref(p), n_chips, n_pix, n_obs,
                                   dates.ctypes.data, spectra.ctypes.data, qa.ctypes.data))
-        self._keep = (dates, spectra, qa)
-        self._n_pix = n_pix
+        self._last = _Staged.uniform((dates, spectra, qa), n_chips, n_pix, n_obs)
 
     def stage_chips(self, batch, params=None):
         """Stage a ChipBatch (or a list of (dates, spectra, qa) chips of any sizes) in one
         batch: ccdgpu_stage_chips."""
         if not isinstance(batch, ChipBatch):
             batch = ChipBatch.from_chips(batch)
-        p = params if isinstance(params, abi.Params) else abi.params_from_dict(params)
+        p = _params(params)
         _check(lib().ccdgpu_stage_chips(self._ctx, ctypes.byref(p), batch.n_chips, batch.n_pix.ctypes.data,
                                         batch.n_obs.ctypes.data, batch.dates.ctypes.data,
                                         batch.spectra.ctypes.data, batch.qa.ctypes.data))
-        self._keep = batch
-        self._n_pix = None
+        self._last = _Staged.of_batch(batch)
         return batch
 
     def stage_slot_chips(self, slot, batch, params=None):
@@ -696,62 +662,45 @@ class Context(object):
         upload asynchronously).  An EncodedBatch goes through stage_slot_encoded."""
         if isinstance(batch, EncodedBatch):
             return self.stage_slot_encoded(slot, batch, params)
-        p = params if isinstance(params, abi.Params) else abi.params_from_dict(params)
+        p = _params(params)
         _check(lib().ccdgpu_stage_slot_chips(self._ctx, int(slot), ctypes.byref(p), batch.n_chips,
                                              batch.n_pix.ctypes.data, batch.n_obs.ctypes.data,
                                              batch.dates.ctypes.data, batch.spectra.ctypes.data,
                                              batch.qa.ctypes.data))
-        if not hasattr(self, '_slot_keep'):
-            self._slot_keep = {}
-        self._slot_keep[int(slot)] = batch
+        self._slots[int(slot)] = _Staged.of_batch(batch)
 
     def stage_slot_encoded(self, slot, batch, params=None):
         """Upload an EncodedBatch into input slot ``slot`` and decode it there on the device (copy
         stream; same life-time rules as stage_slot_chips)."""
-        p = params if isinstance(params, abi.Params) else abi.params_from_dict(params)
+        p = _params(params)
         _check(lib().ccdgpu_stage_slot_encoded(self._ctx, int(slot), ctypes.byref(p), batch.n_chips,
                                                batch.n_pix.ctypes.data, batch.n_obs.ctypes.data,
                                                batch.dates.ctypes.data, batch.buf.ctypes.data,
                                                int(batch.nbytes_encoded)))
-        if not hasattr(self, '_slot_keep'):
-            self._slot_keep = {}
-        self._slot_keep[int(slot)] = batch
+        self._slots[int(slot)] = _Staged.of_batch(batch)
+
+    def _last_batch_coords(self, cx, cy):
+        """(cx, cy) int32 per chip of the last run, which must be of a ChipBatch."""
+        if not self._last.is_batch:
+            raise ValueError('fetch_batch_rows needs a stage_chips / stage_slot_chips batch')
+        return _chip_coords(cx, cy, self._last.n_chips)
 
     def fetch_batch_rows(self, cx, cy, width=100):
         """Rows of every chip of the last run in one device pass and one copy: (row_offsets
         [total_pixels+1], rows abi.ROW_DTYPE, mask bit words uint32 [total_pixels][words] --
         ChipBatch.mask_of(bits, c) is chip c's int8 [n_pix][n_obs] mask)."""
-        batch = self._keep
-        if not isinstance(batch, ChipBatch):
-            raise ValueError('fetch_batch_rows needs a stage_chips / stage_slot_chips batch')
-        cx = np.ascontiguousarray(cx, dtype=np.int32)
-        cy = np.ascontiguousarray(cy, dtype=np.int32)
-        if cx.shape != (batch.n_chips,) or cy.shape != (batch.n_chips,):
-            raise ValueError('cx / cy need one entry per chip (%d)' % batch.n_chips)
+        cx, cy = self._last_batch_coords(cx, cy)
         r = abi.Rows()
-        rc = lib().ccdgpu_fetch_batch_rows(self._ctx, cx.ctypes.data, cy.ctypes.data, int(width), ctypes.byref(r))
-        try:
-            _check(rc)
-            return abi.unpack_rows(r)
-        finally:
-            lib().ccdgpu_rows_free(ctypes.byref(r))
+        return _take(lib().ccdgpu_fetch_batch_rows(self._ctx, cx.ctypes.data, cy.ctypes.data, int(width), ctypes.byref(r)),
+                     r)
 
     def fetch_batch_rows_into(self, cx, cy, bufs, width=100):
         """fetch_batch_rows into ``bufs`` (a RowsBuffers, reused across batches: pinned, so the
         rows and mask words arrive by DMA with no host copy; ccdgpu_fetch_batch_rows_into).
         Returns views of its arrays, valid until its next use."""
-        batch = self._keep
-        if not isinstance(batch, ChipBatch):
-            raise ValueError('fetch_batch_rows needs a stage_chips / stage_slot_chips batch')
-        cx = np.ascontiguousarray(cx, dtype=np.int32)
-        cy = np.ascontiguousarray(cy, dtype=np.int32)
-        if cx.shape != (batch.n_chips,) or cy.shape != (batch.n_chips,):
-            raise ValueError('cx / cy need one entry per chip (%d)' % batch.n_chips)
+        cx, cy = self._last_batch_coords(cx, cy)
         L = lib()
-        if not hasattr(L, 'ccdgpu_fetch_batch_rows_into'):  # (libraries built before it: A/B runs)
-            return self.fetch_batch_rows(cx, cy, width)
-        n_pix = int(batch.pix_off[-1])
-        words = (int(batch.n_obs.max()) + 31) // 32
+        n_pix, words = self._last.total_pixels, self._last.mask_words
         bufs.ensure(n_pix + 1, n_pix * 2, n_pix * words)
         nr = ctypes.c_int64(0)
         for _ in range(2):
@@ -773,24 +722,22 @@ class Context(object):
         ``pinned_empty`` make the upload overlap a running detection)."""
         dates, spectra, qa = _as_inputs(dates, spectra, qa)
         n_chips, n_pix, n_obs = qa.shape
-        p = params if isinstance(params, abi.Params) else abi.params_from_dict(params)
+        p = _params(params)
         _check(lib().ccdgpu_stage_slot(self._ctx, int(slot), ctypes.byref(p), n_chips, n_pix, n_obs,
                                        dates.ctypes.data, spectra.ctypes.data, qa.ctypes.data))
-        if not hasattr(self, '_slot_keep'):
-            self._slot_keep = {}
-        self._slot_keep[int(slot)] = (dates, spectra, qa)
+        self._slots[int(slot)] = _Staged.uniform((dates, spectra, qa), n_chips, n_pix, n_obs)
+
+    def _ran_slot(self, slot):
+        """The last run is now the batch of slot ``slot``."""
+        self._last = self._slots.get(slot, _Staged())
 
     def run_slot(self, slot):
         """Detect the batch of input slot ``slot`` (waits for its upload); fetch / fetch_rows as
         after run().  Returns the kernel seconds."""
-        secs = ctypes.c_double(0.0)
-        rc = lib().ccdgpu_run_slot(self._ctx, int(slot), ctypes.byref(secs))
-        if rc not in (0, abi.E_QA):
-            _check(rc)
-        self.qa_error = rc == abi.E_QA  # results exist; the pixel's procedure is -1 (fetch)
-        self._keep = self._slot_keep.get(int(slot))
-        self._n_pix = None if isinstance(self._keep, ChipBatch) else self._keep[2].shape[1]
-        return secs.value
+        rc, secs = _timed(lib().ccdgpu_run_slot, self._ctx, int(slot))
+        self._finish(rc)
+        self._ran_slot(int(slot))
+        return secs
 
     def run_slot_begin(self, slot):
         """run_slot in halves (ccdgpu_run_slot_begin / _query / _end): launch the detection of
@@ -811,18 +758,12 @@ class Context(object):
         (ccdgpu_run_slot_begin_rows): chip c's rows at (cx[c], cy[c]) land in ``bufs`` (a
         RowsBuffers, grown here to the slot's pixels: offsets, mask words, and rows for
         ``rows_per_pixel`` per pixel); run_slot_end_rows() waits once and returns them."""
-        batch = self._slot_keep.get(int(slot)) if hasattr(self, '_slot_keep') else None
-        if not isinstance(batch, ChipBatch):
+        staged = self._slots.get(int(slot), _Staged())
+        if not staged.is_batch:
             raise ValueError('run_slot_begin_rows needs a stage_slot_chips / stage_slot_encoded batch')
-        cx = np.ascontiguousarray(cx, dtype=np.int32)
-        cy = np.ascontiguousarray(cy, dtype=np.int32)
-        if cx.shape != (batch.n_chips,) or cy.shape != (batch.n_chips,):
-            raise ValueError('cx / cy need one entry per chip (%d)' % batch.n_chips)
-        n_pix = int(batch.pix_off[-1])
-        words = (int(batch.n_obs.max()) + 31) // 32
-        bufs.ensure(n_pix + 1, int(bufs.rows_per_pixel * n_pix) + 64, n_pix * words)
-        rate = bufs.copy_per_pixel if bufs.copy_per_pixel is not None else bufs.rows_per_pixel
-        cap = min(bufs.rows.size, int(rate * n_pix) + 64)
+        cx, cy = _chip_coords(cx, cy, staged.n_chips)
+        n_pix, words = staged.total_pixels, staged.mask_words
+        _, cap = bufs.reserve(n_pix, words)
         _check(lib().ccdgpu_run_slot_begin_rows(self._ctx, int(slot), cx.ctypes.data, cy.ctypes.data, int(width),
                                                 bufs.offsets.ctypes.data, bufs.offsets.size, bufs.rows.ctypes.data,
                                                 cap, bufs.mask.ctypes.data, bufs.mask.size))
@@ -833,40 +774,25 @@ class Context(object):
         """(row_offsets [n_pix+1], rows, mask words [n_pix][words]) of the batch begun with
         run_slot_begin_rows -- views of its RowsBuffers, valid until their next use.  More rows
         than the buffer held: the buffer grows (and learns the rate) and the rows are fetched."""
-        secs = ctypes.c_double(0.0)
         nr = ctypes.c_int64(0)
-        rc = lib().ccdgpu_run_slot_end_rows(self._ctx, ctypes.byref(secs), ctypes.byref(nr))
+        rc, _ = _timed(lib().ccdgpu_run_slot_end_rows, self._ctx, after=(ctypes.byref(nr),))
         cx, cy, bufs, width, n_pix, words, cap = self._rows_req
         self._rows_req = None
-        self._keep = self._slot_keep.get(self._pending_slot)
-        self._n_pix = None
-        if nr.value > 0:
-            bufs.max_rate = max(bufs.max_rate, nr.value / max(1, n_pix))
-            bufs.copy_per_pixel = min(bufs.rows_per_pixel, 1.25 * bufs.max_rate)
-        short = (rc == abi.E_OVERFLOW and 'rows' in last_error()) or rc == abi.E_QA
-        if short and nr.value > cap and self._keep is not None:
-            # the run is complete but its rows did not fit: grow, learn the rate, fetch them (an
-            # unsupported QA value comes back as E_QA with the count set, and still raises)
-            bufs.rows_per_pixel = max(bufs.rows_per_pixel, 1.25 * nr.value / max(1, n_pix))
-            bufs.copy_per_pixel = min(bufs.rows_per_pixel, 1.25 * bufs.max_rate)
+        self._ran_slot(self._pending_slot)
+        # the library sets the count only for a completed run: more rows than the copy held come with
+        # E_OVERFLOW, or with E_QA for a batch that also has an unsupported QA value (it still raises)
+        if bufs.learn(nr.value, n_pix, cap) and rc in (abi.E_OVERFLOW, abi.E_QA) and self._last.keep is not None:
             self.qa_error = rc == abi.E_QA
             return self.fetch_batch_rows_into(cx, cy, bufs, width)
-        if rc not in (0, abi.E_QA):
-            _check(rc)
-        self.qa_error = rc == abi.E_QA
+        self._finish(rc)
         n = nr.value
         return bufs.offsets[:n_pix + 1], bufs.rows[:n], bufs.mask[:n_pix * words].reshape(n_pix, words)
 
     def run_slot_end(self):
-        secs = ctypes.c_double(0.0)
-        rc = lib().ccdgpu_run_slot_end(self._ctx, ctypes.byref(secs))
-        if rc not in (0, abi.E_QA):
-            _check(rc)
-        self.qa_error = rc == abi.E_QA
-        slot = self._pending_slot
-        self._keep = self._slot_keep.get(slot)
-        self._n_pix = None if isinstance(self._keep, ChipBatch) else self._keep[2].shape[1]
-        return secs.value
+        rc, secs = _timed(lib().ccdgpu_run_slot_end, self._ctx)
+        self._finish(rc)
+        self._ran_slot(self._pending_slot)
+        return secs
 
     def stage_chipmunk(self, dates, text, offsets, n_pix, params=None):
         """Stage chips from the chipmunk wire format (see ccdc.chipmunk.pack_text):
@@ -883,59 +809,43 @@ class Context(object):
         if offsets.shape != (n_chips, n_obs, 8):
             raise ValueError('offsets must be [n_chips][n_obs][8], got %r' % (offsets.shape,))
         text = bytes(text)
-        p = params if isinstance(params, abi.Params) else abi.params_from_dict(params)
-        secs = ctypes.c_double(0.0)
-        _check(lib().ccdgpu_stage_chipmunk(self._ctx, ctypes.byref(p), n_chips, int(n_pix), n_obs,
-                                           dates.ctypes.data, text, len(text), offsets.ctypes.data,
-                                           ctypes.byref(secs)))
-        self._keep = (dates, text, offsets)
-        self._n_pix = int(n_pix)
-        return secs.value
+        p = _params(params)
+        rc, secs = _timed(lib().ccdgpu_stage_chipmunk, self._ctx, ctypes.byref(p), n_chips, int(n_pix), n_obs,
+                          dates.ctypes.data, text, len(text), offsets.ctypes.data)
+        _check(rc)
+        self._last = _Staged.uniform((dates, text, offsets), n_chips, int(n_pix), n_obs)
+        return secs
 
     def staged_inputs(self):
         """The staged pixel inputs copied back: (spectra [C][7][n_pix][n], qa [C][n_pix][n]) for
         a uniform batch, flat (spectra, qa) in the ChipBatch layout for a stage_chips batch."""
-        if isinstance(self._keep, ChipBatch):  # (an EncodedBatch too: decoded on the device)
-            b = self._keep
-            nd = int(b.data_off[-1])
+        s = self._last
+        if s.keep is None:
+            raise CcdGpuError(abi.E_INVAL, 'nothing staged')
+        if s.is_batch:  # (an EncodedBatch too: decoded on the device)
+            nd = int((s.n_pix.astype(np.int64) * s.n_obs).sum())
             spectra, qa = np.empty(7 * nd, dtype=np.int16), np.empty(nd, dtype=np.uint16)
-            _check(lib().ccdgpu_staged_inputs(self._ctx, spectra.ctypes.data, qa.ctypes.data))
-            return spectra, qa
-        d = self._keep[0]
-        n_chips, n_obs = d.shape if d.ndim == 2 else (1, d.shape[0])
-        n_pix = self._n_pix
-        spectra = np.empty((n_chips, 7, n_pix, n_obs), dtype=np.int16)
-        qa = np.empty((n_chips, n_pix, n_obs), dtype=np.uint16)
+        else:
+            n_pix, n_obs = int(s.n_pix[0]), int(s.n_obs[0])
+            spectra = np.empty((s.n_chips, 7, n_pix, n_obs), dtype=np.int16)
+            qa = np.empty((s.n_chips, n_pix, n_obs), dtype=np.uint16)
         _check(lib().ccdgpu_staged_inputs(self._ctx, spectra.ctypes.data, qa.ctypes.data))
         return spectra, qa
 
     def run(self):
-        secs = ctypes.c_double(0.0)
-        rc = lib().ccdgpu_run_staged(self._ctx, ctypes.byref(secs))
-        if rc not in (0, abi.E_QA):
-            _check(rc)
-        self.qa_error = rc == abi.E_QA  # results exist; the pixel's procedure is -1 (fetch)
-        return secs.value
+        rc, secs = _timed(lib().ccdgpu_run_staged, self._ctx)
+        self._finish(rc)
+        return secs
 
     def fetch(self, chip):
         res = abi.Result()
-        rc = lib().ccdgpu_fetch_staged(self._ctx, int(chip), ctypes.byref(res))
-        try:
-            _check(rc)
-            return abi.unpack(res)
-        finally:
-            lib().ccdgpu_result_free(ctypes.byref(res))
+        return _take(lib().ccdgpu_fetch_staged(self._ctx, int(chip), ctypes.byref(res)), res)
 
     def fetch_rows(self, chip, cx, cy, width=100):
         """Segment / pixel table rows of staged chip ``chip`` (output writer, packed on the
         device): (row_offsets [n_pix+1], rows abi.ROW_DTYPE [n_rows], mask int8 [n_pix][n_obs])."""
         r = abi.Rows()
-        rc = lib().ccdgpu_fetch_rows(self._ctx, int(chip), int(cx), int(cy), int(width), ctypes.byref(r))
-        try:
-            _check(rc)
-            return abi.unpack_rows(r)
-        finally:
-            lib().ccdgpu_rows_free(ctypes.byref(r))
+        return _take(lib().ccdgpu_fetch_rows(self._ctx, int(chip), int(cx), int(cy), int(width), ctypes.byref(r)), r)
 
     # random-forest classification of segment rows (rfrawp) --------------------------------------
     def set_forest(self, forest):
@@ -954,20 +864,23 @@ class Context(object):
         _check(lib().ccdgpu_forest_clear(self._ctx))
         self._forest_shape = None
 
+    def _forest_dims(self):
+        """(n_features, n_classes) of the forest set."""
+        if self._forest_shape is None:
+            raise CcdGpuError(abi.E_INVAL, 'no forest set (Context.set_forest)')
+        return self._forest_shape
+
     def classify(self, features):
         """features [n_rows][n_features] float64 (ccdc.features.matrix) -> rfrawp float32
         [n_rows][n_classes] (ccdgpu_classify); the kernel seconds are in ``forest_seconds``."""
-        shape = getattr(self, '_forest_shape', None)
-        if shape is None:
-            raise CcdGpuError(abi.E_INVAL, 'no forest set (Context.set_forest)')
-        nf, nc = shape
+        nf, nc = self._forest_dims()
         x = np.ascontiguousarray(features, dtype=np.float64)
         if x.ndim != 2 or x.shape[1] != nf:
             raise ValueError('features must be [n_rows][%d], got %r' % (nf, x.shape))
         out = np.empty((x.shape[0], nc), dtype=np.float32)
-        secs = ctypes.c_double(0.0)
-        _check(lib().ccdgpu_classify(self._ctx, x.ctypes.data, x.shape[0], out.ctypes.data, ctypes.byref(secs)))
-        self.forest_seconds = secs.value
+        rc, secs = _timed(lib().ccdgpu_classify, self._ctx, x.ctypes.data, x.shape[0], out.ctypes.data)
+        _check(rc)
+        self.forest_seconds = secs
         return out
 
     def classify_rows(self, aux, rows_cap=None):
@@ -976,27 +889,19 @@ class Context(object):
         (ccdgpu_classify_rows).  aux [total_pixels][5] float64: dem, aspect, slope, mpw, posidex.
         Rows without a model are NaN.  ``rows_cap`` (tests): the buffer's room instead of a size
         learned from the library."""
-        shape = getattr(self, '_forest_shape', None)
-        if shape is None:
-            raise CcdGpuError(abi.E_INVAL, 'no forest set (Context.set_forest)')
-        nc = shape[1]
+        nc = self._forest_dims()[1]
         a = np.ascontiguousarray(aux, dtype=np.float64)
         if a.ndim != 2 or a.shape[1] != 5:
             raise ValueError('aux must be [total_pixels][5], got %r' % (a.shape,))
-        batch = getattr(self, '_keep', None)
-        n_pix = batch.total_pixels if isinstance(batch, ChipBatch) else None
-        if n_pix is None and batch is not None and getattr(self, '_n_pix', None) is not None:
-            d = np.asarray(batch[0])
-            n_pix = (d.shape[0] if d.ndim == 2 else 1) * self._n_pix
+        n_pix = self._last.total_pixels
         if n_pix is not None and a.shape[0] != n_pix:
             raise ValueError('aux has %d pixels, the batch %d' % (a.shape[0], n_pix))
         nr = ctypes.c_int64(0)
-        secs = ctypes.c_double(0.0)
         L = lib()
         cap = int(rows_cap) if rows_cap is not None else 2 * a.shape[0] + 64
         for _ in range(2):
             out = np.empty((cap, nc), dtype=np.float32)
-            rc = L.ccdgpu_classify_rows(self._ctx, a.ctypes.data, out.ctypes.data, cap, ctypes.byref(nr), ctypes.byref(secs))
+            rc, secs = _timed(L.ccdgpu_classify_rows, self._ctx, a.ctypes.data, out.ctypes.data, cap, ctypes.byref(nr))
             if rc == 0:
                 break
             if rows_cap is not None or rc != abi.E_INVAL or nr.value <= cap:
@@ -1005,7 +910,7 @@ class Context(object):
             cap = nr.value  # more rows than the first guess
         else:
             _check(rc)
-        self.forest_seconds = secs.value
+        self.forest_seconds = secs
         self.forest_rows = nr.value
         return out[:nr.value]
 
@@ -1028,21 +933,15 @@ class Context(object):
         those shapes and types to fill instead of new ones -- the call is the copy of its output, and
         page-locked arrays (``pinned_empty``), reused, receive it by DMA at the link's speed.
         Arguments that fail ccdgpu_predict_check raise CcdGpuError (E_INVAL) with the library's message."""
-        off = np.ascontiguousarray(row_offsets, dtype=np.int64).reshape(-1)
-        r = np.ascontiguousarray(rows, dtype=abi.ROW_DTYPE).reshape(-1)
-        if off.shape[0] < 1:
-            raise ValueError('row_offsets must have n_pix + 1 entries')
+        off, r = _row_table(row_offsets, rows)
         d = _predict_dates(dates)
         cover, dtype = _predict_modes(cover, dtype)
         n_pix = off.shape[0] - 1
-        if int(off[-1]) != r.shape[0]:
-            raise ValueError('row_offsets end at %d, the table has %d rows' % (int(off[-1]), r.shape[0]))
         out, idx = _predict_buffers(out, seg_index, n_pix, d.shape[0], dtype)
-        secs = ctypes.c_double(0.0)
-        _check(lib().ccdgpu_predict(self._ctx, n_pix, off.ctypes.data, r.ctypes.data, d.shape[0], d.ctypes.data,
-                                    float(avg_days_yr), cover, dtype, out.ctypes.data,
-                                    None if idx is None else idx.ctypes.data, ctypes.byref(secs)))
-        self.predict_seconds = secs.value
+        rc, secs = _timed(lib().ccdgpu_predict, self._ctx, n_pix, off.ctypes.data, r.ctypes.data, d.shape[0], d.ctypes.data,
+                          float(avg_days_yr), cover, dtype, out.ctypes.data, _ptr(idx))
+        _check(rc)
+        self.predict_seconds = secs
         return out, idx
 
     def predict_rows(self, chip, dates, avg_days_yr=365.2425, cover='span', dtype='float32', seg_index=True, out=None):
@@ -1051,21 +950,17 @@ class Context(object):
         ``out`` / ``seg_index`` as for ``predict``."""
         d = _predict_dates(dates)
         cover, dtype = _predict_modes(cover, dtype)
-        batch = getattr(self, '_keep', None)
         chip = int(chip)
-        if isinstance(batch, ChipBatch):
-            n_pix = int(batch.n_pix[chip]) if 0 <= chip < batch.n_chips else None
-        else:
-            n_pix = getattr(self, '_n_pix', None)
-        secs = ctypes.c_double(0.0)
-        if n_pix is None:  # nothing staged here, or no such chip: the library names the reason (no buffers passed)
-            _check(lib().ccdgpu_predict_rows(self._ctx, chip, d.shape[0], d.ctypes.data, float(avg_days_yr), cover, dtype,
-                                             None, None, ctypes.byref(secs)))
-            raise CcdGpuError(abi.E_INVAL, 'no completed run to predict from')
+
+        def call(out, idx):
+            rc, secs = _timed(lib().ccdgpu_predict_rows, self._ctx, chip, d.shape[0], d.ctypes.data, float(avg_days_yr),
+                              cover, dtype, _ptr(out), _ptr(idx))
+            _check(rc)
+            return secs
+
+        n_pix = self._chip_pixels(chip, lambda: call(None, None), 'no completed run to predict from')
         out, idx = _predict_buffers(out, seg_index, n_pix, d.shape[0], dtype)
-        _check(lib().ccdgpu_predict_rows(self._ctx, chip, d.shape[0], d.ctypes.data, float(avg_days_yr), cover, dtype,
-                                         out.ctypes.data, None if idx is None else idx.ctypes.data, ctypes.byref(secs)))
-        self.predict_seconds = secs.value
+        self.predict_seconds = call(out, idx)
         return out, idx
 
     # annual change and land-cover product rasters from segments ------------------------------------
@@ -1079,21 +974,15 @@ class Context(object):
         arrays to fill instead of new ones (page-locked ones, ``pinned_empty``, receive them by DMA).
         The kernel seconds are in ``products_seconds``.  Arguments that fail ccdgpu_products_check
         raise CcdGpuError (E_INVAL) with the library's message."""
-        off = np.ascontiguousarray(row_offsets, dtype=np.int64).reshape(-1)
-        r = np.ascontiguousarray(rows, dtype=abi.ROW_DTYPE).reshape(-1)
-        if off.shape[0] < 1:
-            raise ValueError('row_offsets must have n_pix + 1 entries')
-        if int(off[-1]) != r.shape[0]:
-            raise ValueError('row_offsets end at %d, the table has %d rows' % (int(off[-1]), r.shape[0]))
+        off, r = _row_table(row_offsets, rows)
         d = _predict_dates(dates)
         p = product_params(**kw) if params is None else params
         rf = _rfrawp(rfrawp, r.shape[0], p)
         want, arrays, ptrs = _product_request(want, out, off.shape[0] - 1, d.shape[0], rf is not None)
-        secs = ctypes.c_double(0.0)
-        _check(lib().ccdgpu_products(self._ctx, off.shape[0] - 1, off.ctypes.data, r.ctypes.data,
-                                     None if rf is None else rf.ctypes.data, d.shape[0], d.ctypes.data, ctypes.byref(p),
-                                     ctypes.byref(ptrs), ctypes.byref(secs)))
-        self.products_seconds = secs.value
+        rc, secs = _timed(lib().ccdgpu_products, self._ctx, off.shape[0] - 1, off.ctypes.data, r.ctypes.data, _ptr(rf),
+                          d.shape[0], d.ctypes.data, ctypes.byref(p), ctypes.byref(ptrs))
+        _check(rc)
+        self.products_seconds = secs
         return arrays
 
     def products_rows(self, chip, dates, rfrawp=None, params=None, want=None, out=None, **kw):
@@ -1103,31 +992,27 @@ class Context(object):
         products); its row count is checked by the library's offsets, so pass exactly the chip's."""
         d = _predict_dates(dates)
         p = product_params(**kw) if params is None else params
-        batch = getattr(self, '_keep', None)
         chip = int(chip)
-        if isinstance(batch, ChipBatch):
-            n_pix = int(batch.n_pix[chip]) if 0 <= chip < batch.n_chips else None
-        else:
-            n_pix = getattr(self, '_n_pix', None)
-        secs = ctypes.c_double(0.0)
         rf = None
         if rfrawp is not None:
             rf = np.ascontiguousarray(rfrawp, dtype=np.float32)
             rf = _rfrawp(rf, rf.shape[0], p)
-        if n_pix is None:  # nothing staged here, or no such chip: the library names the reason (no buffers passed)
-            ptrs = abi.Products()
-            ptrs.sctime = 1
-            _check(lib().ccdgpu_products_rows(self._ctx, chip, None, 0, None, ctypes.byref(p), ctypes.byref(ptrs),
-                                              ctypes.byref(secs)))
-            raise CcdGpuError(abi.E_INVAL, 'no completed run to make products from')
+
+        def call(rf, n_dates, dates, ptrs):
+            rc, secs = _timed(lib().ccdgpu_products_rows, self._ctx, chip, _ptr(rf), n_dates, dates, ctypes.byref(p),
+                              ctypes.byref(ptrs))
+            _check(rc)
+            return secs
+
+        probe = abi.Products()
+        probe.sctime = 1
+        n_pix = self._chip_pixels(chip, lambda: call(None, 0, None, probe), 'no completed run to make products from')
         want, arrays, ptrs = _product_request(want, out, n_pix, d.shape[0], rf is not None)
         if rf is not None:  # the chip's rows: a row per segment, one for a pixel without any
             n_rows = self.chip_row_count(chip)
             if rf.shape[0] != n_rows:
                 raise ValueError('rfrawp has %d rows, chip %d has %d' % (rf.shape[0], chip, n_rows))
-        _check(lib().ccdgpu_products_rows(self._ctx, chip, None if rf is None else rf.ctypes.data, d.shape[0], d.ctypes.data,
-                                          ctypes.byref(p), ctypes.byref(ptrs), ctypes.byref(secs)))
-        self.products_seconds = secs.value
+        self.products_seconds = call(rf, d.shape[0], d.ctypes.data, ptrs)
         return arrays
 
     def chip_row_count(self, chip):
@@ -1167,7 +1052,7 @@ class _Pinned(object):
 def batch_storage(max_chips, max_pix, max_obs, pinned=True):
     """Reusable buffers for ChipBatch(..., storage=...): room for ``max_chips`` chips of up to
     ``max_pix`` pixels x ``max_obs`` observations."""
-    alloc = pinned_empty if pinned else np.empty
+    alloc = _allocator(pinned)
     n = int(max_chips) * int(max_pix) * int(max_obs)
     return (alloc((int(max_chips) * int(max_obs),), np.int64), alloc((7 * n,), np.int16), alloc((n,), np.uint16))
 
@@ -1193,12 +1078,33 @@ class RowsBuffers(object):
         if arr.size >= n:
             return arr
         n = int(n * 1.25) + 64
-        return pinned_empty((n,), dtype) if self.pinned else np.empty(n, dtype)
+        return _allocator(self.pinned)((n,), dtype)
 
     def ensure(self, n_offsets, n_rows, n_words):
         self.offsets = self._grow(self.offsets, n_offsets, np.int64)
         self.rows = self._grow(self.rows, n_rows, abi.ROW_DTYPE)
         self.mask = self._grow(self.mask, n_words, np.uint32)
+
+    def reserve(self, n_pix, words):
+        """Grow the buffers for a batch chain of ``n_pix`` pixels with ``words`` mask words each
+        (run_slot_begin_rows): returns (the rows room, the rows the chain copies back -- the learned
+        rate's, within the room)."""
+        self.ensure(n_pix + 1, int(self.rows_per_pixel * n_pix) + 64, n_pix * words)
+        rate = self.copy_per_pixel if self.copy_per_pixel is not None else self.rows_per_pixel
+        return self.rows.size, min(self.rows.size, int(rate * n_pix) + 64)
+
+    def learn(self, n_rows, n_pix, cap):
+        """Learn from a finished batch chain of ``n_pix`` pixels that had ``n_rows`` rows and copied
+        ``cap`` back: ``max_rate`` and ``copy_per_pixel`` follow the rate seen; more rows than the copy
+        held also raise ``rows_per_pixel``, and the answer is True: the rows must be fetched."""
+        if n_rows > 0:
+            self.max_rate = max(self.max_rate, n_rows / max(1, n_pix))
+            self.copy_per_pixel = min(self.rows_per_pixel, 1.25 * self.max_rate)
+        if n_rows <= cap:
+            return False
+        self.rows_per_pixel = max(self.rows_per_pixel, 1.25 * n_rows / max(1, n_pix))
+        self.copy_per_pixel = min(self.rows_per_pixel, 1.25 * self.max_rate)
+        return True
 
 
 def pinned_empty(shape, dtype):

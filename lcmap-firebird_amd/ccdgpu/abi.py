@@ -1,7 +1,9 @@
-"""ctypes mirror of include/ccdgpu.h (structs only) and result unpacking helpers.
+"""ctypes mirror of include/ccdgpu.h -- its structs, its constants and, in ``SIGNATURES``, every
+function's return and argument types -- and result unpacking helpers.
 
-The struct layouts here ARE the C-ABI contract of libccdgpu.so; keep them in lock-step with
-include/ccdgpu.h.  ``result_to_pixels`` turns a CSR ``ccdgpu_result`` into the per-pixel
+The struct layouts and the signature table here ARE the C-ABI contract of libccdgpu.so; keep them in
+lock-step with include/ccdgpu.h (tests/test_abi.py parses the header against the table).
+``pixel_result`` turns a CSR ``ccdgpu_result`` into the per-pixel
 ``ccd.detect`` result dicts pyccd returns (consumed by ccdc/pyccd.py:106-148 ``format``).
 """
 import ctypes
@@ -205,6 +207,90 @@ def forest_struct(root, feature, threshold, left, right, value, n_features):
     f.right = right.ctypes.data_as(ctypes.POINTER(_i32))
     f.value = value.ctypes.data_as(ctypes.POINTER(_f64))
     return f, (root, feature, threshold, left, right, value)
+
+
+def _signatures():
+    c = ctypes
+    P = c.POINTER
+    i, i32, i64, u16, dbl, ptr = c.c_int, c.c_int32, c.c_int64, c.c_uint16, c.c_double, c.c_void_p
+    ctx, params, secs, n64 = ptr, P(Params), P(dbl), P(i64)   # ccdgpu_ctx *, const ccdgpu_params *, double *, int64_t *
+    pparams, products = P(ProductParams), P(Products)
+    rows_into = (ptr, i64, ptr, i64, ptr, i64)                # row_offsets, cap, rows, cap, mask_bits, cap
+    encode = (i32, ptr, ptr, ptr, ptr, ptr, i64, i32, u16, u16)
+    return {
+        'ccdgpu_version': (c.c_char_p, ()),
+        'ccdgpu_last_error': (c.c_char_p, ()),
+        'ccdgpu_params_default': (None, (params,)),
+        'ccdgpu_init': (i, (i, P(ptr))),
+        'ccdgpu_init_copy_cus': (i, (i, i, P(ptr))),
+        'ccdgpu_destroy': (i, (ctx,)),
+        'ccdgpu_device_count': (i, (P(i),)),
+        'ccdgpu_device_numa_node': (i, (i, P(i))),
+        'ccdgpu_synchronize': (i, (ctx,)),
+        'ccdgpu_detect_batch': (i, (ctx, params, i32, i32, ptr, ptr, ptr, P(Result))),
+        'ccdgpu_result_free': (None, (P(Result),)),
+        'ccdgpu_stage_chips': (i, (ctx, params, i32, ptr, ptr, ptr, ptr, ptr)),
+        'ccdgpu_stage': (i, (ctx, params, i32, i32, i32, ptr, ptr, ptr)),
+        'ccdgpu_run_staged': (i, (ctx, secs)),
+        'ccdgpu_stage_chipmunk': (i, (ctx, params, i32, i32, i32, ptr, c.c_char_p, i64, ptr, secs)),
+        'ccdgpu_host_alloc': (i, (c.c_size_t, P(ptr))),
+        'ccdgpu_host_free': (i, (ptr,)),
+        'ccdgpu_stage_slot_chips': (i, (ctx, i32, params, i32, ptr, ptr, ptr, ptr, ptr)),
+        'ccdgpu_stage_slot': (i, (ctx, i32, params, i32, i32, i32, ptr, ptr, ptr)),
+        'ccdgpu_run_slot': (i, (ctx, i32, secs)),
+        'ccdgpu_run_slot_begin': (i, (ctx, i32)),
+        'ccdgpu_run_query': (i, (ctx,)),
+        'ccdgpu_run_slot_end': (i, (ctx, secs)),
+        'ccdgpu_run_slot_begin_rows': (i, (ctx, i32, ptr, ptr, i32) + rows_into),
+        'ccdgpu_run_slot_end_rows': (i, (ctx, secs, n64)),
+        'ccdgpu_encoded_bound': (i64, (i32, ptr, ptr)),
+        'ccdgpu_encode_chips': (i64, encode),
+        'ccdgpu_encoded_bound_flags': (i64, (i32, ptr, ptr, c.c_uint32)),
+        'ccdgpu_encode_chips_flags': (i64, encode + (c.c_uint32,)),
+        'ccdgpu_encode_vector_path': (i32, ()),
+        'ccdgpu_encoded_check': (i, (i32, ptr, ptr, ptr, i64)),
+        'ccdgpu_stage_slot_encoded': (i, (ctx, i32, params, i32, ptr, ptr, ptr, ptr, i64)),
+        'ccdgpu_staged_inputs': (i, (ctx, ptr, ptr)),
+        'ccdgpu_fetch_staged': (i, (ctx, i32, P(Result))),
+        'ccdgpu_fetch_rows': (i, (ctx, i32, i32, i32, i32, P(Rows))),
+        'ccdgpu_fetch_batch_rows': (i, (ctx, ptr, ptr, i32, P(Rows))),
+        'ccdgpu_fetch_batch_rows_into': (i, (ctx, ptr, ptr, i32) + rows_into + (n64,)),
+        'ccdgpu_rows_free': (None, (P(Rows),)),
+        'ccdgpu_forest_check': (i, (P(Forest),)),
+        'ccdgpu_forest_depth': (i, (P(Forest), P(i32))),
+        'ccdgpu_forest_set': (i, (ctx, P(Forest))),
+        'ccdgpu_forest_clear': (i, (ctx,)),
+        'ccdgpu_classify': (i, (ctx, ptr, i64, ptr, secs)),
+        'ccdgpu_classify_rows': (i, (ctx, ptr, ptr, i64, n64, secs)),
+        'ccdgpu_predict_check': (i, (i64, ptr, i64, ptr, i64, ptr, dbl, i32, i32)),
+        'ccdgpu_predict': (i, (ctx, i64, ptr, ptr, i64, ptr, dbl, i32, i32, ptr, ptr, secs)),
+        'ccdgpu_predict_rows': (i, (ctx, i32, i64, ptr, dbl, i32, i32, ptr, ptr, secs)),
+        'ccdgpu_coefficient_matrix': (i, (ctx, i64, ptr, dbl, ptr)),
+        'ccdgpu_product_params_default': (None, (pparams,)),
+        'ccdgpu_year_window': (i, (i64, n64, n64)),
+        'ccdgpu_products_check': (i, (i64, ptr, i64, ptr, ptr, i64, ptr, pparams, products)),
+        'ccdgpu_products': (i, (ctx, i64, ptr, ptr, ptr, i64, ptr, pparams, products, secs)),
+        'ccdgpu_products_rows': (i, (ctx, i32, ptr, i64, ptr, pparams, products, secs)),
+        'ccdgpu_chip_row_count': (i, (ctx, i32, n64)),
+        'ccdgpu_last_stats': (i, (ctx, P(Stats))),
+        'ccdgpu_diag_counters': (i, (ctx, P(c.c_uint64), i32)),
+    }
+
+
+# name -> (restype, argtypes) of every function include/ccdgpu.h declares, in header order: array and
+# context pointers are c_void_p (numpy's ``.ctypes.data``), struct and scalar outputs typed pointers
+SIGNATURES = _signatures()
+
+
+def declare(L, signatures):
+    """Set restype / argtypes of library ``L``'s functions from a ``SIGNATURES`` table and return it.  A
+    symbol the library lacks (one built before the symbol: A/B runs) is skipped; calling it raises
+    ctypes' AttributeError naming it."""
+    for name, (restype, argtypes) in signatures.items():
+        fn = getattr(L, name, None)
+        if fn is not None:
+            fn.restype, fn.argtypes = restype, list(argtypes)
+    return L
 
 
 # parameter dict keys (pyccd parameters.yaml names) -> Params fields

@@ -7,6 +7,8 @@ import os
 
 import numpy as np
 
+from . import abi
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_PATH = os.path.join(os.path.dirname(_HERE), 'lib', 'libccdsynth.so')
 
@@ -21,6 +23,19 @@ class SynthCfg(ctypes.Structure):
                 ('seed', ctypes.c_uint64)]
 
 
+_int, _i32, _ptr, _cfg = ctypes.c_int, ctypes.c_int32, ctypes.c_void_p, ctypes.POINTER(SynthCfg)
+# name -> (restype, argtypes) of every function include/ccdsynth.h declares, in header order
+SIGNATURES = {
+    'ccdsynth_config': (_int, (_int, _cfg)),
+    'ccdsynth_dates': (_int, (_cfg, _i32, _ptr, _i32)),
+    'ccdsynth_chip': (_int, (_cfg, _i32, _i32, _i32, _i32, _ptr, _ptr, _ptr)),
+    'ccdsynth_rotate': (_int, (_ptr, _ptr, _i32, _i32, _i32, _ptr, _ptr, _i32)),
+    'ccdsynth_gpu_create': (_int, (_int, ctypes.POINTER(_ptr))),
+    'ccdsynth_gpu_destroy': (None, (_ptr,)),
+    'ccdsynth_gpu_error': (ctypes.c_char_p, ()),
+    'ccdsynth_gpu_batch': (_int, (_ptr, _cfg, _i32) + (_ptr,) * 9),
+}
+
 _lib = None
 
 
@@ -29,20 +44,7 @@ def lib():
     if _lib is None:
         if not os.path.exists(_LIB_PATH):
             raise RuntimeError('libccdsynth.so not built: run __graft_entry__.build()')
-        L = ctypes.CDLL(_LIB_PATH)
-        L.ccdsynth_config.argtypes = [ctypes.c_int, ctypes.POINTER(SynthCfg)]
-        L.ccdsynth_dates.argtypes = [ctypes.POINTER(SynthCfg), ctypes.c_int32,
-                                     ctypes.c_void_p, ctypes.c_int32]
-        L.ccdsynth_chip.argtypes = [ctypes.POINTER(SynthCfg), ctypes.c_int32, ctypes.c_int32,
-                                    ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
-                                    ctypes.c_void_p, ctypes.c_void_p]
-        L.ccdsynth_gpu_create.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]
-        L.ccdsynth_gpu_destroy.argtypes = [ctypes.c_void_p]
-        L.ccdsynth_gpu_error.restype = ctypes.c_char_p
-        L.ccdsynth_gpu_batch.argtypes = [ctypes.c_void_p, ctypes.POINTER(SynthCfg), ctypes.c_int32] + [ctypes.c_void_p] * 9
-        L.ccdsynth_rotate.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32]
-        _lib = L
+        _lib = abi.declare(ctypes.CDLL(_LIB_PATH), SIGNATURES)
     return _lib
 
 

@@ -133,8 +133,8 @@ class SplitOracleContext(OracleContext):
 
 class ChainOracleContext(SplitOracleContext):
     """SplitOracleContext with the device context's batch chain (run_slot_begin_rows /
-    run_slot_end_rows): the rows land in the caller's RowsBuffers, whose rows room is learned
-    from an overflow exactly as ccdgpu.Context does (too small: the rows are fetched after)."""
+    run_slot_end_rows): the rows land in the caller's RowsBuffers, which sizes the copy and learns
+    from an overflow by the methods ccdgpu.Context calls (too small: the rows are fetched after)."""
 
     def __init__(self, device=0, threads=2, run_time=0.05, **kw):
         super(ChainOracleContext, self).__init__(device, threads, run_time, **kw)
@@ -153,11 +153,7 @@ class ChainOracleContext(SplitOracleContext):
     def run_slot_begin_rows(self, slot, cx, cy, bufs, width=100):
         batch = self._slots[slot][0]
         n_pix = int(batch.pix_off[-1])
-        words = (int(batch.n_obs.max()) + 31) // 32
-        bufs.ensure(n_pix + 1, int(bufs.rows_per_pixel * n_pix) + 64, n_pix * words)
-        # the rows the chain copies back: the learned rate, as ccdgpu.Context does
-        rate = bufs.copy_per_pixel if bufs.copy_per_pixel is not None else bufs.rows_per_pixel
-        cap = min(bufs.rows.size, int(rate * n_pix) + 64)
+        _, cap = bufs.reserve(n_pix, (int(batch.n_obs.max()) + 31) // 32)
         self.run_slot_begin(slot)
         self._rows_req = (np.array(cx), np.array(cy), bufs, width, n_pix, cap)
 
@@ -166,11 +162,6 @@ class ChainOracleContext(SplitOracleContext):
         cx, cy, bufs, width, n_pix, cap = self._rows_req
         self.chained += 1
         off, rows, bits = self.fetch_batch_rows(cx, cy, width)
-        if rows.size > 0:
-            bufs.max_rate = max(bufs.max_rate, rows.size / max(1, n_pix))
-            bufs.copy_per_pixel = min(bufs.rows_per_pixel, 1.25 * bufs.max_rate)
-        if rows.size > cap:
+        if bufs.learn(rows.size, n_pix, cap):
             self.overflowed += 1
-            bufs.rows_per_pixel = max(bufs.rows_per_pixel, 1.25 * rows.size / max(1, n_pix))
-            bufs.copy_per_pixel = min(bufs.rows_per_pixel, 1.25 * bufs.max_rate)
         return self.fetch_batch_rows_into(cx, cy, bufs, width)

@@ -194,6 +194,51 @@ def test_upload_slots_match_staged_path(ctx):
         assert np.array_equal(got.mask, ref[i].mask)
 
 
+def test_last_run_shape_follows_every_staging_form(ctx):
+    """One context through every staging form in turn: after each, staged_inputs() gives back exactly
+    what was staged, in the shapes its docstring promises, predict_rows sizes its output by the chip's
+    own pixel count, and a chip past the batch is refused -- the context's record of its last run."""
+    cfg = synth.config(2)
+    chips = [synth.chip(cfg, 0, n_pix=3), synth.chip(cfg, 1, n_pix=5)]  # their own date vectors
+    d0 = chips[0][0]
+    uni = [synth.chip(cfg, c, n_pix=4, chip_dates=d0) for c in (0, 1)]
+    ud, us, uq = d0[None].repeat(2, axis=0), np.stack([u[1] for u in uni]), np.stack([u[2] for u in uni])
+    batch = ccdgpu.ChipBatch.from_chips(chips)
+    when = d0[:3]
+
+    def check(n_pix, spectra, qa):
+        if spectra is not None:
+            s, q = ctx.staged_inputs()
+            assert s.dtype == spectra.dtype and q.dtype == qa.dtype
+            assert s.shape == spectra.shape and q.shape == qa.shape
+            assert np.array_equal(s, spectra) and np.array_equal(q, qa)
+        for c, n in enumerate(n_pix):
+            assert ctx.predict_rows(c, when)[0].shape == (7, n, when.shape[0])
+        with pytest.raises(ccdgpu.CcdGpuError):
+            ctx.predict_rows(len(n_pix), when)
+
+    ctx.stage(ud, us, uq)
+    ctx.run()
+    check([4, 4], us, uq)
+    ctx.stage_slot(0, ud, us, uq)
+    ctx.run_slot(0)
+    check([4, 4], us, uq)
+    ctx.stage_chips(batch)
+    ctx.run()
+    check([3, 5], batch.spectra, batch.qa)
+    ctx.stage_slot(0, ud, us, uq)  # (a uniform batch in between, so the next form has something to replace)
+    ctx.run_slot(0)
+    ctx.stage_slot_chips(1, batch)
+    ctx.run_slot_begin(1)
+    ctx.run_slot_end()
+    check([3, 5], batch.spectra, batch.qa)
+    ctx.stage_slot_chips(2, ccdgpu.EncodedBatch.encode(chips, pinned=False))
+    ctx.run_slot(2)
+    check([3, 5], batch.spectra, batch.qa)
+    ctx.detect_batch(*chips[1])
+    check([5], None, None)
+
+
 def test_concurrent_contexts_on_one_device():
     """Two contexts on one device detecting from two host threads at once (own streams, buffers
     and launch-argument slots) give the same results as one context alone."""

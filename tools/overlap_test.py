@@ -73,7 +73,6 @@ def trial(tag, n_ctx, copy_cus, mode='run'):
                 c.run()
             elif mode == 'fetch':
                 c.run()
-                c._keep = batch
                 c.fetch_batch_rows_into(cx, cx, bufs)
             elif mode == 'runenc':  # encoded inputs read in place, no fetch
                 c.run_slot(i % 3)
