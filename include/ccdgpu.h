@@ -352,8 +352,8 @@ void ccdgpu_rows_free(ccdgpu_rows *out);
 
 /* Random-forest classification of segment rows: the `rfrawp` column of the segment table
  * (resources/schema.cql segment.rfrawp; the reference fills it with Spark ML's
- * RandomForestClassificationModel.rawPrediction, ccdc/randomforest.py:25-39, 500 trees).  Only
- * inference of an imported forest; training stays with Spark.
+ * RandomForestClassificationModel.rawPrediction, ccdc/randomforest.py:25-39, 500 trees).  The
+ * forest is imported, or trained on the device (ccdgpu_forest_train, below).
  *
  * A forest is plain arrays over one node pool.  For one row x[n_features]:
  *     raw[:] = 0.0 (double)
@@ -406,6 +406,92 @@ int ccdgpu_classify(ccdgpu_ctx *ctx, const double *features, int64_t n_rows, flo
  * nothing is written (grow and call again). */
 int ccdgpu_classify_rows(ccdgpu_ctx *ctx, const double *aux, float *rfrawp, int64_t rows_cap, int64_t *n_rows,
                          double *kernel_seconds);
+
+/* Training of the random forest on the device: what the reference does with Spark ML's
+ * RandomForestClassifier over features.dataframe (ccdc/randomforest.py:25-39) -- trees grown over
+ * binned features, level by level, from per-node class histograms.  Parity with Spark ML itself is
+ * not pinned here (no fixture), so the rule below is normative: Spark ML's structure and defaults,
+ * its uncertain choices parameters, built only from integer counts and a counter-based hash.  The
+ * trained forest is a pure function of the inputs: it does not depend on launch shapes, on how the
+ * trees are grouped or on the arrival order of atomic adds; a restatement in numpy is equal array by
+ * array.
+ *
+ * Inputs.  x [n_rows][n_features] double, all finite; labels [n_rows] int32 in 0 .. n_classes-1;
+ * per feature f, n_edges[f] strictly increasing finite doubles, packed back to back in `edges`
+ * (feature f's start at the sum of n_edges before f) -- a feature with n_edges[f] == 0 is never
+ * split; struct ccdgpu_train_params.  Limits: n_rows 1 .. 2^27, n_features 1 ..
+ * CCDGPU_FOREST_MAX_FEATURES, n_classes 1 .. CCDGPU_FOREST_MAX_CLASSES, n_edges[f] 0 ..
+ * CCDGPU_TRAIN_MAX_EDGES (at most 64 bins), n_trees >= 1 with n_trees (2^(max_depth+1) - 1) < 2^31.
+ *
+ * Bins.  bin(r,f) = the number of e in feature f's edges with e < x[r][f]; so x <= edges[f][b]
+ * holds exactly when bin <= b (the inference walk's own test).
+ * Hash.  uint64 arithmetic with wraparound.
+ *     mix(z):    z ^= z>>30; z *= 0xBF58476D1CE4E5B9; z ^= z>>27; z *= 0x94D049BB133111EB; z ^= z>>31
+ *     fold(z,v): mix(z + 0x9E3779B97F4A7C15 + v)
+ *     H(seed,a,b,c) = fold(fold(fold(mix(seed + 0x9E3779B97F4A7C15), a), b), c)
+ * Row weights.  w(t,r) of row r in tree t is 1 when bootstrap == 0.  Otherwise a Poisson(1) draw by
+ *     inverse CDF on integers: u = H(seed,t,r,0) >> 32; w = the number of k with u >= P[k],
+ *     P[k] = floor(2^32 sum_{j<=k} e^-1/j!) for k = 0 .. 12 = CCDGPU_TRAIN_POISSON.  The largest
+ *     weight is 13 (hence n_rows <= 2^27: every count fits 32 bits).
+ * Nodes.  The root is node 1; the children of node i are 2i (left) and 2i+1.
+ * Feature subset of node i of tree t: the m features with the smallest keys H(seed,t,i,1+f), ties
+ *     to the lower f; m = features_per_node clamped to n_features, 0 meaning the smallest m with
+ *     m*m >= n_features (Spark's sqrt); m == n_features: all of them.
+ * Leaf or split.  c_k = the weighted class counts of the node's rows (int64), n = sum c_k,
+ *     q = sum c_k^2.  The node is a leaf when its depth equals max_depth, or q == n*n (pure; an
+ *     integer test), or n < 2 min_instances_per_node, or no candidate is valid.
+ * Candidates.  (f in the subset, b in 0 .. n_edges[f]-1); left counts over the rows with
+ *     bin(r,f) <= b.  Valid iff nL >= min_instances_per_node and nR >= min_instances_per_node and
+ *     gain >= min_info_gain, with the doubles
+ *         score = (double)qL/(double)nL + (double)qR/(double)nR
+ *         gain  = (score - (double)q/(double)n)/(double)n
+ *     each operation one IEEE operation, no contraction.  The chosen candidate has the largest
+ *     score; among equal scores the lowest f, then the lowest b.
+ * A chosen split makes the node an internal node of ccdgpu_forest with feature = f and threshold =
+ *     edges[f][b]; rows with bin <= b go left.
+ * Values.  Every node, internal or leaf, has value[k] = (double)c_k/(double)n.
+ * Empty bag.  n == 0 at a tree's root: the call fails with CCDGPU_EINVAL naming the tree.
+ * Output.  ccdgpu_forest arrays: trees in order, each tree's nodes in pre-order, left before right
+ *     (ccdgpu_forest_check passes by construction). */
+#define CCDGPU_TRAIN_MAX_ROWS ((int64_t)1 << 27)
+#define CCDGPU_TRAIN_MAX_EDGES 63
+#define CCDGPU_TRAIN_MAX_DEPTH 10
+#define CCDGPU_TRAIN_POISSON_N 13
+#define CCDGPU_TRAIN_POISSON                                                                          \
+    { 1580030168u, 3160060337u, 3950075421u, 4213413783u, 4279248373u, 4292415291u, 4294609777u,      \
+      4294923276u, 4294962463u, 4294966817u, 4294967252u, 4294967292u, 4294967295u }
+typedef struct ccdgpu_train_params {
+    int32_t n_trees;                /* 500  (randomforest.py:31 numTrees)                        */
+    int32_t max_depth;              /* 5    0 .. CCDGPU_TRAIN_MAX_DEPTH (Spark's default)         */
+    int32_t features_per_node;      /* 0    0: sqrt; clamped to n_features                       */
+    int32_t min_instances_per_node; /* 1    >= 1                                                 */
+    double min_info_gain;           /* 0.0  >= 0                                                 */
+    int32_t bootstrap;              /* 1    0 or 1                                               */
+    int32_t reserved0;              /* 0                                                         */
+    uint64_t seed;                  /* 0                                                         */
+} ccdgpu_train_params;
+void ccdgpu_train_params_default(ccdgpu_train_params *p);
+/* The checks a training request passes before anything reaches the device (no device needed).  0, or
+ * CCDGPU_EINVAL with the reason in ccdgpu_last_error(), naming the argument and the index: a NULL
+ * array; a count outside the limits above; a non-finite x; a label outside 0 .. n_classes-1; an edge
+ * that is not finite or not above the one before it; a parameter outside its range. */
+int ccdgpu_train_check(const double *x, const int32_t *labels, int64_t n_rows, int32_t n_features, int32_t n_classes,
+                       const double *edges, const int32_t *n_edges, const ccdgpu_train_params *params);
+/* Check, train and keep the result in the context until the next training or ccdgpu_destroy.
+ * Synchronous; *kernel_seconds (may be NULL) gets the device time of the kernels.  The trained forest
+ * is state of its own: it does not replace the context's forest (ccdgpu_forest_set with the fetched
+ * arrays does), and detection and classification are unaffected by it.  The trees are grown in
+ * groups sized by a device-memory budget (CCDGPU_TRAIN_GROUP_TREES in the environment, a test knob,
+ * fixes the group size); the result does not depend on the grouping.  Refused with CCDGPU_EINVAL
+ * while a detection begun with ccdgpu_run_slot_begin is not finished. */
+int ccdgpu_forest_train(ccdgpu_ctx *ctx, const double *x, const int32_t *labels, int64_t n_rows, int32_t n_features,
+                        int32_t n_classes, const double *edges, const int32_t *n_edges, const ccdgpu_train_params *params,
+                        double *kernel_seconds);
+/* The trained forest's tree and node counts (CCDGPU_EINVAL when nothing has been trained), and its
+ * arrays: `into` has n_trees and n_nodes set to those counts and its six pointers at arrays of that
+ * size, which are written; n_features and n_classes are set. */
+int ccdgpu_trained_size(ccdgpu_ctx *ctx, int32_t *n_trees, int32_t *n_nodes);
+int ccdgpu_trained_fetch(ccdgpu_ctx *ctx, ccdgpu_forest *into);
 
 /* Prediction of band values from segment models: the modelled surface reflectance of every pixel
  * at dates of the caller's choosing (pyccd's ccd.models.lasso.predict over coefficient_matrix;

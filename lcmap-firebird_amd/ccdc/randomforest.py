@@ -1,10 +1,12 @@
-"""ccdc.randomforest -- random-forest classification of segments: the ``rfrawp`` column
-(Spark-free mirror of the inference half of reference ccdc/randomforest.py).
+"""ccdc.randomforest -- random-forest training and classification of segments: the ``rfrawp``
+column (Spark-free mirror of reference ccdc/randomforest.py).
 
 The reference trains a Spark ML RandomForestClassifier (500 trees, randomforest.py:25-39) on
 ``features.dataframe`` and keeps the model's ``rawPrediction`` per segment as ``rfrawp``
-(array<float>; ``segment.join`` puts it on the segment rows).  Training stays with Spark.  Here an
-imported forest -- plain arrays, see include/ccdgpu.h -- is evaluated on the device
+(array<float>; ``segment.join`` puts it on the segment rows).  Here ``train`` grows the forest on
+the device over binned features, level by level, by the rule include/ccdgpu.h states
+(ccd_train.hip through ``ccdgpu.Context.train_forest``; ``find_splits`` chooses the bins on the
+host), and a forest -- trained or imported, plain arrays either way -- is evaluated on the device
 (ccd_forest.hip through ``ccdgpu.Context.classify`` / ``classify_rows``); there is no CPU path.
 
 rawPrediction of a row is the sum over the trees, in tree order, of the reached leaf's normalised
@@ -113,6 +115,75 @@ class Forest(object):
     def load(cls, path):
         with np.load(path) as z:
             return cls.from_arrays(*[z[k] for k in _ARRAYS], n_features=int(z['n_features']))
+
+
+def find_splits(matrix, max_bins=32):
+    """Bin edges of the columns of ``matrix`` [n_rows][n_features] (finite values): a list of
+    increasing float64 arrays, one per feature -- Spark ML's rule for continuous features
+    (RandomForest.findSplitsForContinuousFeature, with every row a sample).
+
+    Per column, d_0 < d_1 < .. are its distinct values and n_i their counts.  With at most
+    ``max_bins`` distinct values the edges are the midpoints (d_i + d_{i+1}) / 2 of consecutive
+    distinct values (none for a constant column).  Otherwise there are at most ``max_bins - 1``
+    count-quantile cut points: with stride = n_rows / max_bins, target = stride and c the running
+    count n_0 + .. + n_{i-1}, for i = 1, 2, .. in order: if |c - target| < |c + n_i - target| the
+    midpoint (d_{i-1} + d_i) / 2 is an edge and target grows by stride; then c grows by n_i.  A
+    midpoint equal to the edge before it (neighbouring doubles) is dropped, so the edges strictly
+    increase.  2 <= max_bins <= 64 (the device's bin matrix is uint8 with at most 63 edges)."""
+    x = np.asarray(matrix, dtype=np.float64)
+    if x.ndim != 2:
+        raise ValueError('matrix must be [n_rows][n_features], got %r' % (x.shape,))
+    if not 2 <= int(max_bins) <= 64:
+        raise ValueError('max_bins must be in 2 .. 64, got %r' % (max_bins,))
+    if not np.all(np.isfinite(x)):
+        raise ValueError('matrix holds non-finite values')
+    n_splits = int(max_bins) - 1
+    out = []
+    for f in range(x.shape[1]):
+        d, n = np.unique(x[:, f], return_counts=True)
+        mid = (d[:-1] + d[1:]) / 2.0
+        if d.shape[0] - 1 > n_splits:
+            stride = x.shape[0] / float(n_splits + 1)
+            before = np.cumsum(n)[:-1].tolist()  # the count below d_i, i = 1 ..
+            count = n[1:].tolist()
+            take, target = [], stride
+            for i, (c, k) in enumerate(zip(before, count)):
+                if abs(c - target) < abs(c + k - target):
+                    take.append(i)
+                    target += stride
+            mid = mid[take]
+        if mid.shape[0] > 1:
+            mid = mid[np.concatenate(([True], mid[1:] > mid[:-1]))]
+        out.append(np.ascontiguousarray(mid))
+    return out
+
+
+def train(dataframe, n_trees=500, max_depth=5, max_bins=32, features_per_node='auto', min_instances_per_node=1,
+          min_info_gain=0.0, bootstrap=True, seed=0, context=None):
+    """Train the forest of the reference's ``train`` (randomforest.py:25-39: 500 trees over
+    ``features.dataframe``) on the device and return it as a ``Forest``.  ``dataframe`` is the table of
+    ``features.dataframe``: its ``label`` column (trends[0]) the classes, n_classes = max(label) + 1, its
+    ``features`` column the 33 features.  Rows with a null label or a non-finite feature are dropped;
+    the forest's ``rows_dropped`` / ``rows_trained`` say how many went and stayed.  features_per_node
+    'auto' is every feature for one tree and 'sqrt' otherwise, as Spark's ``featureSubsetStrategy``;
+    'sqrt', 'all' or a count choose directly.  The bins are ``find_splits(matrix, max_bins)``; the other
+    parameters are those of ccdgpu_train_params (include/ccdgpu.h states the rule)."""
+    x = features.matrix(dataframe)
+    label = pc.cast(dataframe['label'], pa.float64()).to_numpy(zero_copy_only=False)
+    keep = np.isfinite(label) & np.all(np.isfinite(x), axis=1)
+    x, y = np.ascontiguousarray(x[keep]), label[keep]
+    if x.shape[0] == 0:
+        raise ValueError('no row with a label and finite features to train on (%d rows dropped)' % keep.shape[0])
+    if np.any(y < 0) or np.any(y != np.floor(y)):
+        raise ValueError('labels must be non-negative integers')
+    if features_per_node == 'auto':
+        features_per_node = 'all' if int(n_trees) == 1 else 'sqrt'
+    forest = _context(context).train_forest(
+        x, y.astype(np.int32), find_splits(x, max_bins), n_trees=n_trees, max_depth=max_depth,
+        features_per_node=features_per_node, min_instances_per_node=min_instances_per_node, min_info_gain=min_info_gain,
+        bootstrap=bool(bootstrap), seed=seed)
+    forest.rows_trained, forest.rows_dropped = int(x.shape[0]), int(keep.shape[0] - x.shape[0])
+    return forest
 
 
 def _context(context):

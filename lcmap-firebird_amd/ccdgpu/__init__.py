@@ -524,6 +524,53 @@ def products_check(row_offsets, rows, dates, rfrawp=None, params=None, want=abi.
         raise ValueError(last_error())
 
 
+def train_params(n_trees=None, max_depth=None, features_per_node=None, min_instances_per_node=None, min_info_gain=None,
+                 bootstrap=None, seed=None):
+    """abi.TrainParams from the library's defaults (ccdgpu_train_params_default: 500 trees, depth 5, the
+    sqrt subset, bootstrap, seed 0) and what is given; features_per_node 0 or 'sqrt' is Spark's sqrt,
+    'all' every feature."""
+    p = abi.TrainParams()
+    lib().ccdgpu_train_params_default(ctypes.byref(p))
+    if features_per_node in ('sqrt', 'all'):
+        features_per_node = 0 if features_per_node == 'sqrt' else abi.FOREST_MAX_FEATURES
+    for name, v in (('n_trees', n_trees), ('max_depth', max_depth), ('features_per_node', features_per_node),
+                    ('min_instances_per_node', min_instances_per_node), ('bootstrap', bootstrap), ('seed', seed)):
+        if v is not None:
+            setattr(p, name, int(v))
+    if min_info_gain is not None:
+        p.min_info_gain = float(min_info_gain)
+    return p
+
+
+def _train_args(x, labels, edges, n_classes, params):
+    """The arguments of ccdgpu_train_check / ccdgpu_forest_train after the context, from array-likes:
+    x [n_rows][n_features], labels [n_rows], edges one sequence per feature (packed back to back for the
+    library), n_classes (None: max(label) + 1), params an abi.TrainParams or a dict for ``train_params``.
+    Returns (arguments, the arrays they point into)."""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    y = np.ascontiguousarray(labels, dtype=np.int32).reshape(-1)
+    if x.ndim != 2 or x.shape[0] != y.shape[0]:
+        raise ValueError('x must be [n_rows][n_features] and labels [n_rows], got %r and %r' % (x.shape, y.shape))
+    if len(edges) != x.shape[1]:
+        raise ValueError('edges must hold one sequence per feature: %d, not %d' % (x.shape[1], len(edges)))
+    per = [np.asarray(e, dtype=np.float64).reshape(-1) for e in edges]
+    n_edges = np.array([e.shape[0] for e in per], dtype=np.int32)
+    flat = np.ascontiguousarray(np.concatenate(per) if per else np.zeros(0), dtype=np.float64)
+    if n_classes is None:
+        n_classes = int(y.max()) + 1 if y.size else 0
+    p = params if isinstance(params, abi.TrainParams) else train_params(**(params or {}))
+    return ((x.ctypes.data, y.ctypes.data, x.shape[0], x.shape[1], int(n_classes), flat.ctypes.data, n_edges.ctypes.data,
+             ctypes.byref(p)), (x, y, flat, n_edges, p))
+
+
+def train_check(x, labels, edges, n_classes=None, **params):
+    """ccdgpu_train_check (no device needed) over array-likes, as ``Context.train_forest`` takes them.
+    Raises ValueError with the library's message."""
+    args, keep = _train_args(x, labels, edges, n_classes, params)  # (keep: alive over the call)
+    if lib().ccdgpu_train_check(*args) != 0:
+        raise ValueError(last_error())
+
+
 class _Staged(object):
     """The shape of a staged batch, one record for every staging form: the host arrays to keep
     alive, the chips' pixel and observation counts, and whether the batch is a ChipBatch (an
@@ -576,7 +623,7 @@ class Context(object):
         self._pending_slot = None  # slot of a run_slot_begin* without its run_slot_end* yet
         self._rows_req = None      # (cx, cy, bufs, width, n_pix, words, cap) of a run_slot_begin_rows
         self._forest_shape = None  # (n_features, n_classes) of the forest set
-        self.forest_seconds = self.predict_seconds = self.products_seconds = 0.0
+        self.forest_seconds = self.train_seconds = self.predict_seconds = self.products_seconds = 0.0
         self.forest_rows = 0
         if copy_cus:
             _check(lib().ccdgpu_init_copy_cus(int(device), int(copy_cus), ctypes.byref(self._ctx)))
@@ -913,6 +960,27 @@ class Context(object):
         self.forest_seconds = secs
         self.forest_rows = nr.value
         return out[:nr.value]
+
+    def train_forest(self, x, labels, edges, n_classes=None, **params):
+        """Train a random forest on the device by the rule of include/ccdgpu.h (ccdgpu_forest_train) and
+        return it as a ccdc.randomforest.Forest: x [n_rows][n_features] float64, labels [n_rows] in
+        0 .. n_classes-1 (n_classes None: max(label) + 1), edges one increasing sequence per feature
+        (``ccdc.randomforest.find_splits``), params the fields of ``train_params``.  The context's own
+        forest (``set_forest``) is untouched; the kernel seconds are in ``train_seconds``.  A request
+        the library refuses raises CcdGpuError with its message."""
+        from ccdc.randomforest import Forest
+        args, keep = _train_args(x, labels, edges, n_classes, params)  # (keep: alive over the call)
+        L = lib()
+        rc, secs = _timed(L.ccdgpu_forest_train, self._ctx, *args)
+        _check(rc)
+        self.train_seconds = secs
+        nt, nn = ctypes.c_int32(0), ctypes.c_int32(0)
+        _check(L.ccdgpu_trained_size(self._ctx, ctypes.byref(nt), ctypes.byref(nn)))
+        nc = args[4]
+        f = Forest(np.empty(nt.value, np.int32), np.empty(nn.value, np.int32), np.empty(nn.value, np.float64),
+                   np.empty(nn.value, np.int32), np.empty(nn.value, np.int32), np.empty((nn.value, nc), np.float64), args[3])
+        _check(L.ccdgpu_trained_fetch(self._ctx, ctypes.byref(f.struct())))
+        return f
 
     # prediction of band values from segment models -----------------------------------------------
     def coefficient_matrix(self, dates, avg_days_yr=365.2425):

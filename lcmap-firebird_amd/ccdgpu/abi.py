@@ -15,6 +15,12 @@ MAX_OBS = 4096
 MAX_PEEK = 96
 FOREST_MAX_FEATURES = 64  # CCDGPU_FOREST_MAX_FEATURES
 FOREST_MAX_CLASSES = 32   # CCDGPU_FOREST_MAX_CLASSES
+TRAIN_MAX_ROWS = 1 << 27   # CCDGPU_TRAIN_MAX_ROWS
+TRAIN_MAX_EDGES = 63       # CCDGPU_TRAIN_MAX_EDGES: edges per feature, so at most 64 bins
+TRAIN_MAX_DEPTH = 10       # CCDGPU_TRAIN_MAX_DEPTH
+# CCDGPU_TRAIN_POISSON: floor(2^32 * CDF of Poisson(1)) at 0 .. 12, the bootstrap weights' table
+TRAIN_POISSON = (1580030168, 3160060337, 3950075421, 4213413783, 4279248373, 4292415291, 4294609777,
+                 4294923276, 4294962463, 4294966817, 4294967252, 4294967292, 4294967295)
 ENC_PACK = 1              # CCDGPU_ENC_PACK: flag of ccdgpu_encode_chips_flags / ccdgpu_encoded_bound_flags
 COVER_SPAN, COVER_EXTEND = 0, 1  # CCDGPU_COVER_*: which row a date takes (include/ccdgpu.h)
 PREDICT_F32, PREDICT_I16 = 0, 1  # CCDGPU_PREDICT_*: output type of a prediction
@@ -185,6 +191,19 @@ class Forest(ctypes.Structure):
                 ('right', ctypes.POINTER(_i32)), ('value', ctypes.POINTER(_f64))]
 
 
+class TrainParams(ctypes.Structure):
+    """ccdgpu_train_params (include/ccdgpu.h)."""
+    _fields_ = [('n_trees', _i32), ('max_depth', _i32), ('features_per_node', _i32), ('min_instances_per_node', _i32),
+                ('min_info_gain', _f64), ('bootstrap', _i32), ('reserved0', _i32), ('seed', ctypes.c_uint64)]
+
+
+def default_train_params():
+    p = TrainParams()
+    p.n_trees, p.max_depth, p.features_per_node, p.min_instances_per_node = 500, 5, 0, 1
+    p.min_info_gain, p.bootstrap, p.seed = 0.0, 1, 0
+    return p
+
+
 def forest_struct(root, feature, threshold, left, right, value, n_features):
     """(abi.Forest, the arrays it points into) from array-likes; the sizes come from the arrays
     (value [n_nodes][n_classes]).  Keep the arrays alive while the struct is in use."""
@@ -214,7 +233,8 @@ def _signatures():
     P = c.POINTER
     i, i32, i64, u16, dbl, ptr = c.c_int, c.c_int32, c.c_int64, c.c_uint16, c.c_double, c.c_void_p
     ctx, params, secs, n64 = ptr, P(Params), P(dbl), P(i64)   # ccdgpu_ctx *, const ccdgpu_params *, double *, int64_t *
-    pparams, products = P(ProductParams), P(Products)
+    pparams, products, tparams = P(ProductParams), P(Products), P(TrainParams)
+    train = (ptr, ptr, i64, i32, i32, ptr, ptr, tparams)      # x, labels, n_rows, n_features, n_classes, edges, n_edges, params
     rows_into = (ptr, i64, ptr, i64, ptr, i64)                # row_offsets, cap, rows, cap, mask_bits, cap
     encode = (i32, ptr, ptr, ptr, ptr, ptr, i64, i32, u16, u16)
     return {
@@ -262,6 +282,11 @@ def _signatures():
         'ccdgpu_forest_clear': (i, (ctx,)),
         'ccdgpu_classify': (i, (ctx, ptr, i64, ptr, secs)),
         'ccdgpu_classify_rows': (i, (ctx, ptr, ptr, i64, n64, secs)),
+        'ccdgpu_train_params_default': (None, (tparams,)),
+        'ccdgpu_train_check': (i, train),
+        'ccdgpu_forest_train': (i, (ctx,) + train + (secs,)),
+        'ccdgpu_trained_size': (i, (ctx, P(i32), P(i32))),
+        'ccdgpu_trained_fetch': (i, (ctx, P(Forest))),
         'ccdgpu_predict_check': (i, (i64, ptr, i64, ptr, i64, ptr, dbl, i32, i32)),
         'ccdgpu_predict': (i, (ctx, i64, ptr, ptr, i64, ptr, dbl, i32, i32, ptr, ptr, secs)),
         'ccdgpu_predict_rows': (i, (ctx, i32, i64, ptr, dbl, i32, i32, ptr, ptr, secs)),

@@ -381,6 +381,70 @@ int products_check_params(const ccdgpu_product_params *p, const float *rfrawp, c
 
 int products_check_dates(int64_t n_dates, const int64_t *dates) { return check_dates("products", n_dates, dates); }
 
+int train_validate(const double *x, const int32_t *labels, int64_t n_rows, int32_t n_features, int32_t n_classes,
+                   const double *edges, const int32_t *n_edges, const ccdgpu_train_params *p) {
+    const std::string who = "train: ";
+    if (!p) return fail(CCDGPU_EINVAL, who + "params is NULL");
+    if (!x) return fail(CCDGPU_EINVAL, who + "x is NULL");
+    if (!labels) return fail(CCDGPU_EINVAL, who + "labels is NULL");
+    if (!n_edges) return fail(CCDGPU_EINVAL, who + "n_edges is NULL");
+    if (n_rows < 1 || n_rows > CCDGPU_TRAIN_MAX_ROWS)
+        return fail(CCDGPU_EINVAL, who + "n_rows must be in [1, 2^27], got " + std::to_string(n_rows));
+    if (n_features < 1 || n_features > CCDGPU_FOREST_MAX_FEATURES)
+        return fail(CCDGPU_EINVAL, who + "n_features must be in [1, " + std::to_string(CCDGPU_FOREST_MAX_FEATURES) + "], got " +
+                                       std::to_string(n_features));
+    if (n_classes < 1 || n_classes > CCDGPU_FOREST_MAX_CLASSES)
+        return fail(CCDGPU_EINVAL, who + "n_classes must be in [1, " + std::to_string(CCDGPU_FOREST_MAX_CLASSES) + "], got " +
+                                       std::to_string(n_classes));
+    if (p->max_depth < 0 || p->max_depth > CCDGPU_TRAIN_MAX_DEPTH)
+        return fail(CCDGPU_EINVAL, who + "max_depth must be in [0, " + std::to_string(CCDGPU_TRAIN_MAX_DEPTH) + "], got " +
+                                       std::to_string(p->max_depth));
+    if (p->n_trees < 1 || p->n_trees > INT32_MAX / ((2 << p->max_depth) - 1))
+        return fail(CCDGPU_EINVAL, who + "n_trees must be in [1, " + std::to_string(INT32_MAX / ((2 << p->max_depth) - 1)) +
+                                       "] at max_depth " + std::to_string(p->max_depth) + ", got " + std::to_string(p->n_trees));
+    if (p->features_per_node < 0)
+        return fail(CCDGPU_EINVAL, who + "features_per_node must be >= 0, got " + std::to_string(p->features_per_node));
+    if (p->min_instances_per_node < 1)
+        return fail(CCDGPU_EINVAL, who + "min_instances_per_node must be >= 1, got " + std::to_string(p->min_instances_per_node));
+    if (!std::isfinite(p->min_info_gain) || p->min_info_gain < 0.0)
+        return fail(CCDGPU_EINVAL, who + "min_info_gain must be finite and >= 0, got " + std::to_string(p->min_info_gain));
+    if (p->bootstrap != 0 && p->bootstrap != 1)
+        return fail(CCDGPU_EINVAL, who + "bootstrap must be 0 or 1, got " + std::to_string(p->bootstrap));
+    int64_t total_edges = 0;
+    for (int32_t f = 0; f < n_features; ++f) {
+        if (n_edges[f] < 0 || n_edges[f] > CCDGPU_TRAIN_MAX_EDGES)
+            return fail(CCDGPU_EINVAL, who + "n_edges[" + std::to_string(f) + "] must be in [0, " +
+                                           std::to_string(CCDGPU_TRAIN_MAX_EDGES) + "], got " + std::to_string(n_edges[f]));
+        total_edges += n_edges[f];
+    }
+    if (total_edges > 0 && !edges) return fail(CCDGPU_EINVAL, who + "edges is NULL");
+    for (int32_t f = 0, at = 0; f < n_features; at += n_edges[f], ++f)
+        for (int32_t b = 0; b < n_edges[f]; ++b) {
+            if (!std::isfinite(edges[at + b]))
+                return fail(CCDGPU_EINVAL, who + "edges of feature " + std::to_string(f) + ": edge " + std::to_string(b) +
+                                               " is not finite");
+            if (b > 0 && !(edges[at + b] > edges[at + b - 1]))
+                return fail(CCDGPU_EINVAL, who + "edges of feature " + std::to_string(f) + ": edge " + std::to_string(b) +
+                                               " is not above edge " + std::to_string(b - 1));
+        }
+    for (int64_t r = 0; r < n_rows; ++r)
+        if (labels[r] < 0 || labels[r] >= n_classes)
+            return fail(CCDGPU_EINVAL, who + "labels[" + std::to_string(r) + "] = " + std::to_string(labels[r]) +
+                                           " is outside 0 .. " + std::to_string(n_classes - 1));
+    for (int64_t i = 0, n = n_rows * n_features; i < n; ++i)
+        if (!std::isfinite(x[i]))
+            return fail(CCDGPU_EINVAL, who + "x[" + std::to_string(i / n_features) + "][" + std::to_string(i % n_features) +
+                                           "] is not finite");
+    return 0;
+}
+
+int32_t train_features_per_node(int32_t n_features, const ccdgpu_train_params *p) {
+    int32_t m = p->features_per_node;
+    if (m == 0)
+        while (m * m < n_features) ++m;
+    return m < n_features ? m : n_features;
+}
+
 }  // namespace ccdhost
 
 using namespace ccdhost;
@@ -446,6 +510,20 @@ int ccdgpu_forest_depth(const ccdgpu_forest *f, int32_t *max_depth) {
     if (!max_depth) return fail(CCDGPU_EINVAL, "NULL argument");
     *max_depth = 0;
     return forest_validate(f, max_depth);
+}
+
+void ccdgpu_train_params_default(ccdgpu_train_params *p) {
+    if (!p) return;
+    *p = ccdgpu_train_params{};
+    p->n_trees = 500;
+    p->max_depth = 5;
+    p->min_instances_per_node = 1;
+    p->bootstrap = 1;
+}
+
+int ccdgpu_train_check(const double *x, const int32_t *labels, int64_t n_rows, int32_t n_features, int32_t n_classes,
+                       const double *edges, const int32_t *n_edges, const ccdgpu_train_params *params) {
+    return train_validate(x, labels, n_rows, n_features, n_classes, edges, n_edges, params);
 }
 
 int ccdgpu_predict_check(int64_t n_pix, const int64_t *row_offsets, int64_t n_rows, const ccdgpu_row *rows, int64_t n_dates,

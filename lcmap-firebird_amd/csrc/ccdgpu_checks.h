@@ -46,6 +46,12 @@ int forest_validate(const ccdgpu_forest *f, int32_t *max_depth);
 int forest_build(const ccdgpu_forest *f, int32_t cap, std::vector<unsigned char> &pool, std::vector<int64_t> &tree_off,
                  std::vector<int32_t> &chunk_first);
 
+// The checks of ccdgpu_train_check, and the m of the rule's feature subsets (features_per_node with
+// 0 resolved to the smallest m with m * m >= n_features, clamped to n_features).
+int train_validate(const double *x, const int32_t *labels, int64_t n_rows, int32_t n_features, int32_t n_classes,
+                   const double *edges, const int32_t *n_edges, const ccdgpu_train_params *p);
+int32_t train_features_per_node(int32_t n_features, const ccdgpu_train_params *p);
+
 int predict_check_dates(int64_t n_dates, const int64_t *dates, double avg_days_yr);
 int predict_check_modes(int32_t cover, int32_t dtype);
 

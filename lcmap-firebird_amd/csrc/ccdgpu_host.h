@@ -1,5 +1,5 @@
 // ccdgpu_host.h -- what the host API's units share (ccdgpu_api.cpp: contexts, staging, detection,
-// row chain and fetches; ccdgpu_forest.cpp; ccdgpu_predict.cpp; ccdgpu_products.cpp): the owners of device memory,
+// row chain and fetches; ccdgpu_forest.cpp; ccdgpu_train.cpp; ccdgpu_predict.cpp; ccdgpu_products.cpp): the owners of device memory,
 // pinned memory and events, and the context.  Private to csrc/.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -79,6 +79,14 @@ struct Event {
     }
     hipError_t create(unsigned flags = hipEventDefault) { return e ? hipSuccess : hipEventCreateWithFlags(&e, flags); }
     operator hipEvent_t() const { return e; }
+};
+
+// The forest of the last ccdgpu_forest_train (ccdgpu_train.cpp): the ccdgpu_forest arrays, on the host.
+struct Trained {
+    bool has = false;
+    int32_t n_features = 0, n_classes = 0;
+    std::vector<int32_t> root, feature, left, right;
+    std::vector<double> threshold, value;
 };
 
 }  // namespace ccdhost
@@ -191,6 +199,8 @@ struct ccdgpu_ctx {
     DevBuf<double> f_x, f_aux;
     DevBuf<float> f_out;
     Event f_ev[2];
+    // the forest trained last (ccdgpu_forest_train); not the context's forest until it is set
+    ccdhost::Trained trained;
     // prediction of band values (ccd_predict.hip): pixels whose output the device holds at a time
     // (CCDGPU_PREDICT_SLAB_PIXELS, test knob; 0: as many as keep a slab within PREDICT_SLAB_BYTES)
     // and the scratch of a slab -- dates, basis, offsets, table rows, values, row indices
