@@ -493,6 +493,49 @@ int ccdgpu_forest_train(ccdgpu_ctx *ctx, const double *x, const int32_t *labels,
 int ccdgpu_trained_size(ccdgpu_ctx *ctx, int32_t *n_trees, int32_t *n_nodes);
 int ccdgpu_trained_fetch(ccdgpu_ctx *ctx, ccdgpu_forest *into);
 
+/* Out-of-bag evaluation of a forest: every row scored only by the trees whose bag it is not in.
+ * The bags are not stored: w(t,r) of the training rule above is a function of (seed, t, r), so
+ * "row r is out of tree t's bag" is recomputed wherever it is needed.
+ *
+ * The rule.  For the context's forest (ccdgpu_forest_set), a seed, and row i of x with hash index
+ * r = first_row + i:
+ *     raw[:] = 0.0 (double); n = 0
+ *     for t = 0 .. n_trees-1, in this order:
+ *         u = H(seed, t, r, 0) >> 32
+ *         if u >= P[0]: continue          (P = CCDGPU_TRAIN_POISSON; u < P[0]  <=>  w(t,r) == 0)
+ *         walk tree t as ccdgpu_classify does; raw[:] += value[leaf][:]; n += 1
+ *     oob_raw[i][:] = (float) raw[:]      (round to nearest);   n_oob[i] = n
+ * Double adds in tree order and one float rounding, as rfrawp: only the tree set differs per row,
+ * and a restatement in numpy is equal array by array.  A row with n_oob == 0 gets zeros, not NaN:
+ * the count says it was not scored.  The rule holds for any checked forest and any seed, not only
+ * for a trained forest and its own seed (with them, and first_row the row's index in the training
+ * matrix, it is the out-of-bag estimate).  A NaN feature value goes right, as in the walk.
+ * Limits: first_row >= 0, n_rows >= 0, first_row + n_rows <= CCDGPU_TRAIN_MAX_ROWS.  The result of
+ * a row does not depend on how rows are batched: rows [a, b) with first_row = a are the slice of
+ * the whole call. */
+typedef struct ccdgpu_oob_params {
+    uint64_t seed;              /* the training request's seed                              */
+    int64_t first_row;          /* hash index of row 0 of x                                 */
+} ccdgpu_oob_params;
+#define CCDGPU_OOB_CUT 1580030168u /* CCDGPU_TRAIN_POISSON[0]: u below it is a weight of 0 */
+/* The checks an out-of-bag request passes before anything reaches the device (no device needed).
+ * 0, or CCDGPU_EINVAL with the reason in ccdgpu_last_error(), naming the argument: params NULL; a
+ * count outside the limits above; with n_rows > 0, a NULL array.  x is not scanned: the walk
+ * defines what a NaN does. */
+int ccdgpu_oob_check(const double *x, int64_t n_rows, const ccdgpu_oob_params *params, const float *oob_raw,
+                     const int32_t *n_oob);
+/* x [n_rows][n_features] -> oob_raw [n_rows][n_classes], n_oob [n_rows] by the rule above, in slabs
+ * of rows like ccdgpu_classify.  Synchronous; *kernel_seconds (may be NULL) gets the device time of
+ * the kernel.  n_rows == 0 succeeds without a launch; CCDGPU_EINVAL with no forest set, and while a
+ * detection begun with ccdgpu_run_slot_begin is not finished.  The context's forest, the trained
+ * forest and the last run are untouched. */
+int ccdgpu_forest_oob(ccdgpu_ctx *ctx, const double *x, int64_t n_rows, const ccdgpu_oob_params *params, float *oob_raw,
+                      int32_t *n_oob, double *kernel_seconds);
+/* The trained forest's weighted class counts, the c_k of the training rule: counts
+ * [n_nodes][n_classes] in the node order of ccdgpu_trained_fetch (value[k] = c_k / n there).
+ * CCDGPU_EINVAL when nothing has been trained, or when cap < n_nodes * n_classes. */
+int ccdgpu_trained_counts(ccdgpu_ctx *ctx, int64_t *counts, int64_t cap);
+
 /* Prediction of band values from segment models: the modelled surface reflectance of every pixel
  * at dates of the caller's choosing (pyccd's ccd.models.lasso.predict over coefficient_matrix;
  * annual composites, synthetic images, residuals of observations against their model).

@@ -8,6 +8,8 @@ the device over binned features, level by level, by the rule include/ccdgpu.h st
 (ccd_train.hip through ``ccdgpu.Context.train_forest``; ``find_splits`` chooses the bins on the
 host), and a forest -- trained or imported, plain arrays either way -- is evaluated on the device
 (ccd_forest.hip through ``ccdgpu.Context.classify`` / ``classify_rows``); there is no CPU path.
+A trained forest is judged by ``oob`` -- every row scored on the device only by the trees whose bag
+it was not in (``Context.forest_oob``), summed up by ``evaluation`` -- and ``feature_importances``.
 
 rawPrediction of a row is the sum over the trees, in tree order, of the reached leaf's normalised
 class distribution, indexed by label.  A Spark ``RandomForestClassificationModel`` maps to the
@@ -16,6 +18,7 @@ arrays tree by tree (``model.trees``): an InternalNode gives ``feature = split.f
 children; a LeafNode gives ``feature = -1`` and ``value = impurityStats.stats / sum(stats)``;
 numbering each tree's nodes in pre-order satisfies the child > parent rule of the check.
 """
+import collections
 import ctypes
 
 import numpy as np
@@ -31,7 +34,12 @@ _ARRAYS = ('root', 'feature', 'threshold', 'left', 'right', 'value')
 class Forest(object):
     """A forest as the arrays of ccdgpu_forest: root [n_trees], feature / threshold / left /
     right [n_nodes] (feature < 0 marks a leaf), value [n_nodes][n_classes] (leaves' normalised
-    class distributions)."""
+    class distributions).  A forest trained here (``ccdgpu.Context.train_forest``) also carries
+    ``counts`` int64 [n_nodes][n_classes] (the weighted class counts ``value`` is made of), ``seed`` and
+    ``bootstrap``: what ``oob`` and ``feature_importances`` need.  They are None on any other forest,
+    and ``save`` does not keep them."""
+
+    counts = seed = bootstrap = None
 
     def __init__(self, root, feature, threshold, left, right, value, n_features):
         from ccdgpu import abi
@@ -159,7 +167,7 @@ def find_splits(matrix, max_bins=32):
 
 
 def train(dataframe, n_trees=500, max_depth=5, max_bins=32, features_per_node='auto', min_instances_per_node=1,
-          min_info_gain=0.0, bootstrap=True, seed=0, context=None):
+          min_info_gain=0.0, bootstrap=True, seed=0, context=None, oob=False):
     """Train the forest of the reference's ``train`` (randomforest.py:25-39: 500 trees over
     ``features.dataframe``) on the device and return it as a ``Forest``.  ``dataframe`` is the table of
     ``features.dataframe``: its ``label`` column (trends[0]) the classes, n_classes = max(label) + 1, its
@@ -167,7 +175,11 @@ def train(dataframe, n_trees=500, max_depth=5, max_bins=32, features_per_node='a
     the forest's ``rows_dropped`` / ``rows_trained`` say how many went and stayed.  features_per_node
     'auto' is every feature for one tree and 'sqrt' otherwise, as Spark's ``featureSubsetStrategy``;
     'sqrt', 'all' or a count choose directly.  The bins are ``find_splits(matrix, max_bins)``; the other
-    parameters are those of ccdgpu_train_params (include/ccdgpu.h states the rule)."""
+    parameters are those of ccdgpu_train_params (include/ccdgpu.h states the rule).  With ``oob`` the
+    forest also gets ``forest.oob``: the out-of-bag ``Evaluation`` over the kept rows, in their order
+    (``oob`` below; it needs ``bootstrap`` and leaves the trained forest set as the context's)."""
+    if oob and not bootstrap:
+        raise ValueError('oob needs bootstrap: without it every bag is every row and no tree is out of bag')
     x = features.matrix(dataframe)
     label = pc.cast(dataframe['label'], pa.float64()).to_numpy(zero_copy_only=False)
     keep = np.isfinite(label) & np.all(np.isfinite(x), axis=1)
@@ -178,17 +190,122 @@ def train(dataframe, n_trees=500, max_depth=5, max_bins=32, features_per_node='a
         raise ValueError('labels must be non-negative integers')
     if features_per_node == 'auto':
         features_per_node = 'all' if int(n_trees) == 1 else 'sqrt'
-    forest = _context(context).train_forest(
+    ctx = _context(context)
+    forest = ctx.train_forest(
         x, y.astype(np.int32), find_splits(x, max_bins), n_trees=n_trees, max_depth=max_depth,
         features_per_node=features_per_node, min_instances_per_node=min_instances_per_node, min_info_gain=min_info_gain,
         bootstrap=bool(bootstrap), seed=seed)
     forest.rows_trained, forest.rows_dropped = int(x.shape[0]), int(keep.shape[0] - x.shape[0])
+    if oob:
+        forest.oob = _oob(forest, x, y.astype(np.int32), context=ctx)
     return forest
 
 
 def _context(context):
     import ccdgpu
     return context or ccdgpu.default_context()
+
+
+Evaluation = collections.namedtuple('Evaluation', ['raw', 'n_oob', 'predicted', 'confusion', 'rows_scored', 'accuracy',
+                                                   'producers', 'users'])
+Evaluation.__doc__ = """What ``evaluation`` returns: ``raw`` float32 [n][n_classes] and ``n_oob`` int32 [n] as given (the
+trees that scored each row), ``predicted`` int64 [n] (-1: not scored), ``confusion`` int64
+[label][predicted] over the scored rows, ``rows_scored``, ``accuracy``, and per class ``producers``
+(recall: of the rows with that label, the share predicted so) and ``users`` (precision: of the rows
+predicted so, the share with that label); a ratio with a zero denominator is NaN."""
+
+
+def evaluation(raw, n_scored, labels, n_classes):
+    """The ``Evaluation`` of raw predictions ``raw`` [n][n_classes] against ``labels`` [n] in 0 ..
+    n_classes-1, over the rows with ``n_scored`` > 0 (pure numpy).  The predicted class of a scored row
+    is the argmax of its float32 values, a tie going to the lower class; a row no tree scored is
+    predicted -1 and counts nowhere."""
+    raw = np.asarray(raw, dtype=np.float32)
+    n_oob = np.asarray(n_scored, dtype=np.int32).reshape(-1)
+    y = np.asarray(labels).reshape(-1)
+    nc = int(n_classes)
+    if raw.ndim != 2 or raw.shape[1] != nc or not raw.shape[0] == n_oob.shape[0] == y.shape[0]:
+        raise ValueError('raw must be [n][%d] with n_scored [n] and labels [n], got %r, %r and %r'
+                         % (nc, raw.shape, n_oob.shape, y.shape))
+    if y.size and (np.any(y != np.floor(y)) or y.min() < 0 or y.max() >= nc):
+        raise ValueError('labels must be integers in 0 .. %d' % (nc - 1))
+    y = y.astype(np.int64)
+    scored = n_oob > 0
+    predicted = np.where(scored, np.argmax(raw, axis=1), -1).astype(np.int64)  # argmax: the first of the largest
+    confusion = np.bincount(y[scored] * nc + predicted[scored], minlength=nc * nc).astype(np.int64).reshape(nc, nc)
+    hit = np.diagonal(confusion).astype(np.float64)
+    rows_scored = int(scored.sum())
+    with np.errstate(divide='ignore', invalid='ignore'):
+        accuracy = float(np.float64(hit.sum()) / np.float64(rows_scored))
+        producers = hit / confusion.sum(axis=1).astype(np.float64)
+        users = hit / confusion.sum(axis=0).astype(np.float64)
+    return Evaluation(raw, n_oob, predicted, confusion, rows_scored, accuracy, producers, users)
+
+
+def oob(forest, x, labels, seed=None, first_row=0, context=None):
+    """The out-of-bag ``Evaluation`` of ``forest`` over x [n_rows][n_features] and ``labels`` [n_rows]:
+    every row is scored on the device only by the trees whose bag it was not in (include/ccdgpu.h states
+    the rule; ccd_forest.hip through ``ccdgpu.Context.forest_oob``), so the accuracy is an estimate for
+    rows the forest has not seen, which the accuracy on the training rows is not.  x and labels are the
+    training matrix and its labels in the training order -- or rows [first_row, first_row + n_rows) of
+    them: the bag of a row is a function of (seed, tree, row index) and nothing is stored for it.
+    ``seed`` None takes the forest's own (a forest trained here has one).  Sets ``forest`` as the
+    context's forest.  ValueError for a forest trained without bootstrap (every bag is every row, so no
+    tree is out of bag), or without a seed when none is given."""
+    if forest.bootstrap is not None and not forest.bootstrap:
+        raise ValueError('the forest was trained without bootstrap: every bag is every row and no tree is out of bag')
+    if seed is None:
+        seed = forest.seed
+    if seed is None:
+        raise ValueError('the forest has no seed (it was not trained here): give the seed its bags were drawn with')
+    ctx = _context(context)
+    ctx.set_forest(forest)
+    raw, n_oob = ctx.forest_oob(x, seed, first_row)
+    return evaluation(raw, n_oob, labels, forest.n_classes)
+
+
+_oob = oob  # (``train`` has a flag of this name)
+
+
+def feature_importances(forest):
+    """Spark ML's ``featureImportances`` of a forest trained here, float64 [n_features], on the host from
+    ``forest.counts`` (ValueError without them).  With c_k a node's counts, n = sum c_k and q = sum c_k^2
+    (integers), the training rule's numerator ``score - q/n`` is gain * n, Spark's term of a split.  Per
+    tree, over its internal nodes in pre-order, imp[feature] +=
+    ((double)qL/(double)nL + (double)qR/(double)nR) - (double)q/(double)n with L and R the node's
+    children; s = the sum of imp in feature order, added one by one; if s > 0, imp /= s.  The trees'
+    vectors are added in tree order and the total is normalised the same way."""
+    if forest.counts is None:
+        raise ValueError('the forest has no counts (it was not trained here): feature_importances needs forest.counts')
+    counts = np.asarray(forest.counts, dtype=np.int64)
+    if counts.shape != (forest.n_nodes, forest.n_classes):
+        raise ValueError('counts must be [%d][%d], got %r' % (forest.n_nodes, forest.n_classes, counts.shape))
+    n = [int(v) for v in counts.sum(axis=1)]
+    q = [int(v) for v in (counts * counts).sum(axis=1)]
+    feature, left, right = forest.feature.tolist(), forest.left.tolist(), forest.right.tolist()
+    if 0 in n:
+        raise ValueError('node %d has no counts' % n.index(0))
+
+    def normalised(imp):
+        s = 0.0
+        for v in imp.tolist():
+            s += v
+        return imp / s if s > 0 else imp
+
+    total = np.zeros(forest.n_features, dtype=np.float64)
+    for r in forest.root.tolist():
+        imp = np.zeros(forest.n_features, dtype=np.float64)
+        stack = [r]
+        while stack:
+            i = stack.pop()
+            if feature[i] < 0:
+                continue
+            a, b = left[i], right[i]
+            imp[feature[i]] += (float(q[a]) / float(n[a]) + float(q[b]) / float(n[b])) - float(q[i]) / float(n[i])
+            stack.append(b)
+            stack.append(a)  # popped first: the left subtree precedes the right
+        total += normalised(imp)
+    return normalised(total)
 
 
 def predictions(aux, segments, forest, context=None):

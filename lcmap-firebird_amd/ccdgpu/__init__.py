@@ -623,7 +623,7 @@ class Context(object):
         self._pending_slot = None  # slot of a run_slot_begin* without its run_slot_end* yet
         self._rows_req = None      # (cx, cy, bufs, width, n_pix, words, cap) of a run_slot_begin_rows
         self._forest_shape = None  # (n_features, n_classes) of the forest set
-        self.forest_seconds = self.train_seconds = self.predict_seconds = self.products_seconds = 0.0
+        self.forest_seconds = self.train_seconds = self.predict_seconds = self.products_seconds = self.oob_seconds = 0.0
         self.forest_rows = 0
         if copy_cus:
             _check(lib().ccdgpu_init_copy_cus(int(device), int(copy_cus), ctypes.byref(self._ctx)))
@@ -980,7 +980,32 @@ class Context(object):
         f = Forest(np.empty(nt.value, np.int32), np.empty(nn.value, np.int32), np.empty(nn.value, np.float64),
                    np.empty(nn.value, np.int32), np.empty(nn.value, np.int32), np.empty((nn.value, nc), np.float64), args[3])
         _check(L.ccdgpu_trained_fetch(self._ctx, ctypes.byref(f.struct())))
+        # what the out-of-bag estimate and the importances need (not persisted by Forest.save)
+        f.counts = np.empty((nn.value, nc), np.int64)
+        _check(L.ccdgpu_trained_counts(self._ctx, f.counts.ctypes.data, f.counts.size))
+        p = keep[-1]
+        f.seed, f.bootstrap = int(p.seed), bool(p.bootstrap)
         return f
+
+    def forest_oob(self, x, seed, first_row=0):
+        """The out-of-bag walk of include/ccdgpu.h (ccdgpu_forest_oob) of x [n_rows][n_features] float64
+        through the forest set: row i, with hash index first_row + i, is scored only by the trees whose
+        bag under ``seed`` it is not in.  Returns (oob_raw float32 [n_rows][n_classes], n_oob int32
+        [n_rows]: the trees that scored the row; 0: the row is all zeros); the kernel seconds are in
+        ``oob_seconds``.  A request the library refuses raises CcdGpuError with its message."""
+        nf, nc = self._forest_dims()
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if x.ndim != 2 or x.shape[1] != nf:
+            raise ValueError('x must be [n_rows][%d], got %r' % (nf, x.shape))
+        p = abi.OobParams()
+        p.seed, p.first_row = int(seed), int(first_row)
+        raw = np.empty((x.shape[0], nc), dtype=np.float32)
+        n_oob = np.empty(x.shape[0], dtype=np.int32)
+        rc, secs = _timed(lib().ccdgpu_forest_oob, self._ctx, x.ctypes.data, x.shape[0], ctypes.byref(p), raw.ctypes.data,
+                          n_oob.ctypes.data)
+        _check(rc)
+        self.oob_seconds = secs
+        return raw, n_oob
 
     # prediction of band values from segment models -----------------------------------------------
     def coefficient_matrix(self, dates, avg_days_yr=365.2425):

@@ -21,6 +21,7 @@ TRAIN_MAX_DEPTH = 10       # CCDGPU_TRAIN_MAX_DEPTH
 # CCDGPU_TRAIN_POISSON: floor(2^32 * CDF of Poisson(1)) at 0 .. 12, the bootstrap weights' table
 TRAIN_POISSON = (1580030168, 3160060337, 3950075421, 4213413783, 4279248373, 4292415291, 4294609777,
                  4294923276, 4294962463, 4294966817, 4294967252, 4294967292, 4294967295)
+OOB_CUT = TRAIN_POISSON[0]  # CCDGPU_OOB_CUT: a draw below it is a weight of 0, the row is out of the bag
 ENC_PACK = 1              # CCDGPU_ENC_PACK: flag of ccdgpu_encode_chips_flags / ccdgpu_encoded_bound_flags
 COVER_SPAN, COVER_EXTEND = 0, 1  # CCDGPU_COVER_*: which row a date takes (include/ccdgpu.h)
 PREDICT_F32, PREDICT_I16 = 0, 1  # CCDGPU_PREDICT_*: output type of a prediction
@@ -197,6 +198,11 @@ class TrainParams(ctypes.Structure):
                 ('min_info_gain', _f64), ('bootstrap', _i32), ('reserved0', _i32), ('seed', ctypes.c_uint64)]
 
 
+class OobParams(ctypes.Structure):
+    """ccdgpu_oob_params (include/ccdgpu.h)."""
+    _fields_ = [('seed', ctypes.c_uint64), ('first_row', ctypes.c_int64)]
+
+
 def default_train_params():
     p = TrainParams()
     p.n_trees, p.max_depth, p.features_per_node, p.min_instances_per_node = 500, 5, 0, 1
@@ -233,7 +239,7 @@ def _signatures():
     P = c.POINTER
     i, i32, i64, u16, dbl, ptr = c.c_int, c.c_int32, c.c_int64, c.c_uint16, c.c_double, c.c_void_p
     ctx, params, secs, n64 = ptr, P(Params), P(dbl), P(i64)   # ccdgpu_ctx *, const ccdgpu_params *, double *, int64_t *
-    pparams, products, tparams = P(ProductParams), P(Products), P(TrainParams)
+    pparams, products, tparams, oparams = P(ProductParams), P(Products), P(TrainParams), P(OobParams)
     train = (ptr, ptr, i64, i32, i32, ptr, ptr, tparams)      # x, labels, n_rows, n_features, n_classes, edges, n_edges, params
     rows_into = (ptr, i64, ptr, i64, ptr, i64)                # row_offsets, cap, rows, cap, mask_bits, cap
     encode = (i32, ptr, ptr, ptr, ptr, ptr, i64, i32, u16, u16)
@@ -287,6 +293,9 @@ def _signatures():
         'ccdgpu_forest_train': (i, (ctx,) + train + (secs,)),
         'ccdgpu_trained_size': (i, (ctx, P(i32), P(i32))),
         'ccdgpu_trained_fetch': (i, (ctx, P(Forest))),
+        'ccdgpu_oob_check': (i, (ptr, i64, oparams, ptr, ptr)),
+        'ccdgpu_forest_oob': (i, (ctx, ptr, i64, oparams, ptr, ptr, secs)),
+        'ccdgpu_trained_counts': (i, (ctx, ptr, i64)),
         'ccdgpu_predict_check': (i, (i64, ptr, i64, ptr, i64, ptr, dbl, i32, i32)),
         'ccdgpu_predict': (i, (ctx, i64, ptr, ptr, i64, ptr, dbl, i32, i32, ptr, ptr, secs)),
         'ccdgpu_predict_rows': (i, (ctx, i32, i64, ptr, dbl, i32, i32, ptr, ptr, secs)),

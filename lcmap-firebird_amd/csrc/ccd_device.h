@@ -148,6 +148,11 @@ int32_t ccdk_forest_chunk_cap(int32_t n_features);
 // a flagged row is not walked and gets NaN
 int ccdk_forest_classify(const CcdForestDev *f, const double *x, const unsigned char *skip, int64_t n_rows, float *out,
                          void *stream);
+// out-of-bag walk (include/ccdgpu.h states the rule): row i of x, hash index first_row + i, is scored
+// by the trees t with fold(fold(tree_key[t], r), 0) >> 32 < CCDGPU_OOB_CUT; tree_key [n_trees]
+// (device) = ccd_train_hash_a(seed, t).  out [n_rows][n_classes], n_oob [n_rows] the trees that scored
+int ccdk_forest_oob(const CcdForestDev *f, const double *x, const uint64_t *tree_key, int64_t first_row, int64_t n_rows,
+                    float *out, int32_t *n_oob, void *stream);
 // feature matrix of a run's rows (ccdgpu_classify_rows): pixel p's rows row_off[p] .. from its
 // segments seg[seg_off[p] ..] (one default row, flagged in skip, without any) and aux[p][5];
 // n_seg / n_rows bound the segment reads and the row writes

@@ -15,11 +15,15 @@
 // larger than a chunk is walked from global memory (L2) by the same code.  A node is 16 bytes
 // (threshold, feature, left child; the right child is the next node), read as one b128; the
 // leaves' class vectors follow the nodes of their tree, so a chunk carries them too.
+//
+// ccd_forest_oob is the same walk for the out-of-bag estimate: a row takes only the trees whose bag
+// it is not in, by the training rule's hash (ccd_train.h).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/ccdgpu.h"
 #include "ccd_device.h"
+#include "ccd_train.h"
 
 namespace {
 
@@ -103,6 +107,78 @@ __global__ __launch_bounds__(T) void ccd_forest_classify(CcdForestDev f, const d
     }
 }
 
+constexpr uint32_t POISSON[CCDGPU_TRAIN_POISSON_N] = CCDGPU_TRAIN_POISSON;
+static_assert(POISSON[0] == CCDGPU_OOB_CUT, "CCDGPU_OOB_CUT is the first entry of CCDGPU_TRAIN_POISSON");
+
+// The out-of-bag walk (include/ccdgpu.h states the rule): ccd_forest_classify's layout -- one lane
+// per row, feature vectors transposed in LDS, the trees streamed through LDS in chunks -- with the
+// rule's membership test in front of every tree.  tree_key[t] = ccd_train_hash_a(seed, t) is the same
+// for every lane (a scalar load per tree); the lane folds its hash index r and 0 into it and walks the
+// tree only when the draw is below CCDGPU_OOB_CUT, i.e. when w(t, r) == 0.  The count of trees that
+// scored the row stays in a register.  Rows past n_rows neither read nor write.
+template <int NC, int T>
+__global__ __launch_bounds__(T) void ccd_forest_oob(CcdForestDev f, const double *__restrict__ x,
+                                                    const uint64_t *__restrict__ tree_key, uint64_t first_row, int64_t n_rows,
+                                                    float *__restrict__ out, int32_t *__restrict__ n_oob) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    constexpr int XS = T + 1;
+    const int nf = f.n_features, nc = f.n_classes;
+    double *xs = reinterpret_cast<double *>(smem);
+    unsigned char *chunk = smem + feat_bytes(nf, T);
+    const int tid = (int)threadIdx.x;
+    const int64_t row0 = (int64_t)blockIdx.x * T;
+    if (row0 >= n_rows) return;
+    const int nrow = n_rows - row0 < T ? (int)(n_rows - row0) : T;
+    const double *xb = x + row0 * nf;
+    for (int i = tid; i < nrow * nf; i += T) {
+        const int r = i / nf, c = i - r * nf;
+        xs[c * XS + r] = xb[i];
+    }
+    const int64_t row = row0 + tid;
+    const bool live = tid < nrow;
+    const uint64_t r = first_row + (uint64_t)row;
+    double acc[NC];
+#pragma unroll
+    for (int k = 0; k < NC; ++k) acc[k] = 0.0;
+    int32_t scored = 0;
+    const double *xs_lane = xs + tid;
+    // out of tree t's bag: the draw u = H(seed, t, r, 0) >> 32 is below P[0]
+    auto out_of_bag = [&](int t) {
+        return live && (uint32_t)(ccd_train_fold(ccd_train_fold(tree_key[t], r), 0) >> 32) < CCDGPU_OOB_CUT;
+    };
+    for (int c = 0; c < f.n_chunks; ++c) {
+        const int t0 = f.chunk_first[c], t1 = f.chunk_first[c + 1];
+        const int64_t base = f.tree_off[t0];
+        const int64_t bytes = f.tree_off[t1] - base;
+        if (bytes <= (int64_t)f.chunk_cap) {
+            __syncthreads();  // the feature vectors are in place / the previous chunk is done with
+            const uint4 *src = reinterpret_cast<const uint4 *>(f.pool + base);
+            uint4 *dst = reinterpret_cast<uint4 *>(chunk);
+            for (int i = tid; i < (int)(bytes >> 4); i += T) dst[i] = src[i];
+            __syncthreads();
+            for (int t = t0; t < t1; ++t)
+                if (out_of_bag(t)) {
+                    walk<NC>(chunk + (f.tree_off[t] - base), xs_lane, XS, f.max_depth, nc, acc);
+                    ++scored;
+                }
+        } else {
+            __syncthreads();  // (the feature vectors, when this is the first chunk)
+            for (int t = t0; t < t1; ++t)
+                if (out_of_bag(t)) {
+                    walk<NC>(f.pool + f.tree_off[t], xs_lane, XS, f.max_depth, nc, acc);
+                    ++scored;
+                }
+        }
+    }
+    if (live) {
+        float *o = out + row * nc;
+#pragma unroll
+        for (int k = 0; k < NC; ++k)
+            if (k < nc) o[k] = __double2float_rn(acc[k]);
+        n_oob[row] = scored;
+    }
+}
+
 // The feature matrix of a run's rows, one wave per pixel, lanes over the elements of its rows:
 // the float32 value the row packer stores (ccd_rows.hip) widened to double, then the pixel's aux
 // values.  n_seg / n_rows bound every read and write.
@@ -157,6 +233,32 @@ int launch_nc(const CcdForestDev &f, const double *x, const unsigned char *skip,
     return launch<32, T>(f, x, skip, n_rows, out, s);
 }
 
+// the same launch shape for the out-of-bag walk
+template <int NC, int T>
+int launch_oob(const CcdForestDev &f, const double *x, const uint64_t *tree_key, int64_t first_row, int64_t n_rows, float *out,
+               int32_t *n_oob, hipStream_t s) {
+    const int lds = feat_bytes(f.n_features, T) + f.chunk_cap;
+    if (lds > LDS_BYTES || f.chunk_cap < 16) return -1;
+    auto k = ccd_forest_oob<NC, T>;
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
+        return -1;
+    const int64_t blocks = (n_rows + T - 1) / T;
+    if (blocks <= 0 || blocks > 0x7fffffff) return -1;
+    hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(T), lds, s, f, x, tree_key, (uint64_t)first_row, n_rows, out, n_oob);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+template <int T>
+int launch_oob_nc(const CcdForestDev &f, const double *x, const uint64_t *tree_key, int64_t first_row, int64_t n_rows,
+                  float *out, int32_t *n_oob, hipStream_t s) {
+    const int nc = f.n_classes;
+    if (nc <= 2) return launch_oob<2, T>(f, x, tree_key, first_row, n_rows, out, n_oob, s);
+    if (nc <= 4) return launch_oob<4, T>(f, x, tree_key, first_row, n_rows, out, n_oob, s);
+    if (nc <= 9) return launch_oob<9, T>(f, x, tree_key, first_row, n_rows, out, n_oob, s);
+    if (nc <= 16) return launch_oob<16, T>(f, x, tree_key, first_row, n_rows, out, n_oob, s);
+    return launch_oob<32, T>(f, x, tree_key, first_row, n_rows, out, n_oob, s);
+}
+
 }  // namespace
 
 // Rows per block: 512 where the feature vectors of 512 rows leave a chunk's room in LDS (up to 35
@@ -187,6 +289,17 @@ extern "C" int ccdk_forest_classify(const CcdForestDev *f, const double *x, cons
         return -1;
     if (f->threads == 512) return launch_nc<512>(*f, x, skip, n_rows, out, (hipStream_t)stream);
     if (f->threads == 256) return launch_nc<256>(*f, x, skip, n_rows, out, (hipStream_t)stream);
+    return -1;
+}
+
+extern "C" int ccdk_forest_oob(const CcdForestDev *f, const double *x, const uint64_t *tree_key, int64_t first_row,
+                               int64_t n_rows, float *out, int32_t *n_oob, void *stream) {
+    if (n_rows <= 0) return 0;
+    if (f->n_classes < 1 || f->n_classes > CCDGPU_FOREST_MAX_CLASSES || f->n_features < 1 ||
+        f->n_features > CCDGPU_FOREST_MAX_FEATURES || first_row < 0)
+        return -1;
+    if (f->threads == 512) return launch_oob_nc<512>(*f, x, tree_key, first_row, n_rows, out, n_oob, (hipStream_t)stream);
+    if (f->threads == 256) return launch_oob_nc<256>(*f, x, tree_key, first_row, n_rows, out, n_oob, (hipStream_t)stream);
     return -1;
 }
 

@@ -445,6 +445,21 @@ int32_t train_features_per_node(int32_t n_features, const ccdgpu_train_params *p
     return m < n_features ? m : n_features;
 }
 
+int oob_validate(const double *x, int64_t n_rows, const ccdgpu_oob_params *p, const float *oob_raw, const int32_t *n_oob) {
+    const std::string who = "oob: ";
+    if (!p) return fail(CCDGPU_EINVAL, who + "params is NULL");
+    if (n_rows < 0 || n_rows > CCDGPU_TRAIN_MAX_ROWS)
+        return fail(CCDGPU_EINVAL, who + "n_rows must be in [0, 2^27], got " + std::to_string(n_rows));
+    if (p->first_row < 0 || p->first_row > CCDGPU_TRAIN_MAX_ROWS - n_rows)
+        return fail(CCDGPU_EINVAL, who + "first_row must be in [0, 2^27 - n_rows], got " + std::to_string(p->first_row) +
+                                       " with " + std::to_string(n_rows) + " rows");
+    if (n_rows == 0) return 0;
+    if (!x) return fail(CCDGPU_EINVAL, who + "x is NULL");
+    if (!oob_raw) return fail(CCDGPU_EINVAL, who + "oob_raw is NULL");
+    if (!n_oob) return fail(CCDGPU_EINVAL, who + "n_oob is NULL");
+    return 0;
+}
+
 }  // namespace ccdhost
 
 using namespace ccdhost;
@@ -524,6 +539,11 @@ void ccdgpu_train_params_default(ccdgpu_train_params *p) {
 int ccdgpu_train_check(const double *x, const int32_t *labels, int64_t n_rows, int32_t n_features, int32_t n_classes,
                        const double *edges, const int32_t *n_edges, const ccdgpu_train_params *params) {
     return train_validate(x, labels, n_rows, n_features, n_classes, edges, n_edges, params);
+}
+
+int ccdgpu_oob_check(const double *x, int64_t n_rows, const ccdgpu_oob_params *params, const float *oob_raw,
+                     const int32_t *n_oob) {
+    return oob_validate(x, n_rows, params, oob_raw, n_oob);
 }
 
 int ccdgpu_predict_check(int64_t n_pix, const int64_t *row_offsets, int64_t n_rows, const ccdgpu_row *rows, int64_t n_dates,

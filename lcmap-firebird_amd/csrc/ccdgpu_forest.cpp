@@ -2,6 +2,7 @@
 // ccd_forest.hip; the forest's checks and its device form in ccdgpu_checks.cpp).
 #include <algorithm>
 
+#include "ccd_train.h"
 #include "ccdgpu_host.h"
 
 using namespace ccdhost;
@@ -17,6 +18,7 @@ int ccdgpu_forest_clear(ccdgpu_ctx *c) {
     (void)hipSetDevice(c->device);
     c->has_forest = false;
     c->forest = CcdForestDev{};
+    c->f_n_trees = 0;
     c->f_pool.release();
     c->f_tree_off.release();
     c->f_chunk_first.release();
@@ -53,6 +55,7 @@ int ccdgpu_forest_set(ccdgpu_ctx *c, const ccdgpu_forest *f) {
     c->forest.max_depth = max_depth;
     c->forest.threads = ccdk_forest_threads(f->n_features);
     c->forest.chunk_cap = cap;
+    c->f_n_trees = f->n_trees;
     c->has_forest = true;
     return 0;
 }
@@ -82,6 +85,46 @@ int ccdgpu_classify(ccdgpu_ctx *c, const double *features, int64_t n_rows, float
         }
         HIPCHK(hipEventRecord(c->f_ev[1], ax));
         HIPCHK(hipMemcpyAsync(rfrawp + r0 * nc, c->f_out.p, sizeof(float) * (size_t)(n * nc), hipMemcpyDeviceToHost, ax));
+        HIPCHK(hipStreamSynchronize(ax));
+        float ms = 0.f;
+        (void)hipEventElapsedTime(&ms, c->f_ev[0], c->f_ev[1]);
+        secs += ms * 1e-3;
+    }
+    if (kernel_seconds) *kernel_seconds = secs;
+    return 0;
+}
+
+int ccdgpu_forest_oob(ccdgpu_ctx *c, const double *x, int64_t n_rows, const ccdgpu_oob_params *p, float *oob_raw, int32_t *n_oob,
+                      double *kernel_seconds) {
+    if (kernel_seconds) *kernel_seconds = 0.0;
+    if (!c) return fail(CCDGPU_EINVAL, "NULL ctx");
+    if (!c->has_forest) return fail(CCDGPU_EINVAL, "no forest set (ccdgpu_forest_set)");
+    int rc = busy(c);
+    if (rc || (rc = oob_validate(x, n_rows, p, oob_raw, n_oob))) return rc;
+    if (n_rows == 0) return 0;
+    HIPCHK(hipSetDevice(c->device));
+    const int64_t nf = c->forest.n_features, nc = c->forest.n_classes;
+    const int64_t slab = std::min(n_rows, FOREST_SLAB);
+    // the per-tree prefix of the rule's hash, once per call
+    std::vector<uint64_t> keys((size_t)c->f_n_trees);
+    for (int32_t t = 0; t < c->f_n_trees; ++t) keys[t] = ccd_train_hash_a(p->seed, (uint64_t)t);
+    if ((rc = c->f_x.ensure((size_t)(slab * nf))) || (rc = c->f_out.ensure((size_t)(slab * nc))) ||
+        (rc = c->f_noob.ensure((size_t)slab)) || (rc = c->f_keys.ensure(keys.size())))
+        return rc;
+    hipStream_t ax = c->aux;
+    HIPCHK(hipMemcpyAsync(c->f_keys.p, keys.data(), sizeof(uint64_t) * keys.size(), hipMemcpyHostToDevice, ax));
+    double secs = 0.0;
+    for (int64_t r0 = 0; r0 < n_rows; r0 += slab) {
+        const int64_t n = std::min(slab, n_rows - r0);
+        HIPCHK(hipMemcpyAsync(c->f_x.p, x + r0 * nf, sizeof(double) * (size_t)(n * nf), hipMemcpyHostToDevice, ax));
+        HIPCHK(hipEventRecord(c->f_ev[0], ax));
+        if (ccdk_forest_oob(&c->forest, c->f_x.p, c->f_keys.p, p->first_row + r0, n, c->f_out.p, c->f_noob.p, ax)) {
+            (void)hipStreamSynchronize(ax);
+            return fail(CCDGPU_EHIP, "forest kernel launch failed");
+        }
+        HIPCHK(hipEventRecord(c->f_ev[1], ax));
+        HIPCHK(hipMemcpyAsync(oob_raw + r0 * nc, c->f_out.p, sizeof(float) * (size_t)(n * nc), hipMemcpyDeviceToHost, ax));
+        HIPCHK(hipMemcpyAsync(n_oob + r0, c->f_noob.p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, ax));
         HIPCHK(hipStreamSynchronize(ax));
         float ms = 0.f;
         (void)hipEventElapsedTime(&ms, c->f_ev[0], c->f_ev[1]);

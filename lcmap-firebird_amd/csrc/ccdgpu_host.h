@@ -81,12 +81,14 @@ struct Event {
     operator hipEvent_t() const { return e; }
 };
 
-// The forest of the last ccdgpu_forest_train (ccdgpu_train.cpp): the ccdgpu_forest arrays, on the host.
+// The forest of the last ccdgpu_forest_train (ccdgpu_train.cpp): the ccdgpu_forest arrays, on the host,
+// and the nodes' weighted class counts [n_nodes][n_classes] (the c_k that value is made of).
 struct Trained {
     bool has = false;
     int32_t n_features = 0, n_classes = 0;
     std::vector<int32_t> root, feature, left, right;
     std::vector<double> threshold, value;
+    std::vector<int64_t> counts;
 };
 
 }  // namespace ccdhost
@@ -199,6 +201,11 @@ struct ccdgpu_ctx {
     DevBuf<double> f_x, f_aux;
     DevBuf<float> f_out;
     Event f_ev[2];
+    // the out-of-bag walk (ccdgpu_forest_oob): the forest's tree count, and per call the trees' hash
+    // keys and a slab's counts of scoring trees
+    int32_t f_n_trees = 0;
+    DevBuf<uint64_t> f_keys;
+    DevBuf<int32_t> f_noob;
     // the forest trained last (ccdgpu_forest_train); not the context's forest until it is set
     ccdhost::Trained trained;
     // prediction of band values (ccd_predict.hip): pixels whose output the device holds at a time

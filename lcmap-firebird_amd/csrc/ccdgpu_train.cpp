@@ -255,7 +255,10 @@ int ccdgpu_forest_train(ccdgpu_ctx *c, const double *x, const int32_t *labels, i
                 const uint32_t *cn = &grown.counts[at * nc];
                 int64_t n, q;
                 sums(cn, nc, &n, &q);
-                for (int32_t k = 0; k < nc; ++k) out.value.push_back((double)cn[k] / (double)n);
+                for (int32_t k = 0; k < nc; ++k) {
+                    out.value.push_back((double)cn[k] / (double)n);
+                    out.counts.push_back((int64_t)cn[k]);
+                }
                 if (f >= 0) {
                     stack.push_back({2 * id + 1, me});
                     stack.push_back({2 * id, me});  // popped first: the left subtree precedes the right
@@ -297,6 +300,18 @@ int ccdgpu_trained_fetch(ccdgpu_ctx *c, ccdgpu_forest *into) {
     std::copy(t.value.begin(), t.value.end(), const_cast<double *>(into->value));
     into->n_features = t.n_features;
     into->n_classes = t.n_classes;
+    return 0;
+}
+
+int ccdgpu_trained_counts(ccdgpu_ctx *c, int64_t *counts, int64_t cap) {
+    if (!c) return fail(CCDGPU_EINVAL, "NULL ctx");
+    if (!counts) return fail(CCDGPU_EINVAL, "NULL argument");
+    const Trained &t = c->trained;
+    if (!t.has) return fail(CCDGPU_EINVAL, "no trained forest (ccdgpu_forest_train)");
+    if (cap < (int64_t)t.counts.size())
+        return fail(CCDGPU_EINVAL, "trained_counts: the array holds " + std::to_string(cap) + " counts, the trained forest has " +
+                                       std::to_string(t.counts.size()));
+    std::copy(t.counts.begin(), t.counts.end(), counts);
     return 0;
 }
 
