@@ -536,6 +536,57 @@ int ccdgpu_forest_oob(ccdgpu_ctx *ctx, const double *x, int64_t n_rows, const cc
  * CCDGPU_EINVAL when nothing has been trained, or when cap < n_nodes * n_classes. */
 int ccdgpu_trained_counts(ccdgpu_ctx *ctx, int64_t *counts, int64_t cap);
 
+/* Out-of-bag permutation importances of a forest (Breiman; R randomForest's MeanDecreaseAccuracy):
+ * per tree, how many of the rows out of its bag it votes right, and how many of those votes are lost
+ * or gained when one feature's column is shuffled.  Every output is an integer count.
+ *
+ * The rule.  For the context's forest (ccdgpu_forest_set), x [n_rows][n_features] (the whole training
+ * matrix in training order: row i has hash index i, and the donors below come from all of it), labels
+ * [n_rows] in 0 .. n_classes-1, a training seed and a perm_seed, with n = n_rows:
+ *   vote(t, v): walk tree t over the feature vector v as ccdgpu_classify does (a NaN goes right); at
+ *       the leaf, the lowest k with the largest value[leaf][k] (doubles compared as they are).
+ *   out of bag: H(seed, t, r, 0) >> 32 < CCDGPU_OOB_CUT, the test of ccdgpu_forest_oob.
+ *   the permutation of column f for tree t, a bijection of 0 .. n-1:
+ *       k  = H(perm_seed, t, f, 2^32)      (the last argument is beyond every value training uses)
+ *       b  = (k >> 32) mod n;   a0 = (k & 0xffffffff) mod n
+ *       a  = the first of a0, a0+1, .. (wrapping from n-1 to 0) with gcd(a, n) == 1
+ *       donor(t, f, r) = (a*r + b) mod n   (uint64; the product stays below 2^55)
+ *     n == 1 gives a = 0 and donor 0.  The column is permuted over all rows, not only those out of
+ *     the bag; only the rows out of the bag are evaluated.
+ *   for every tree t and every row r out of t's bag, with y = labels[r]:
+ *       oob_rows[t][y] += 1
+ *       base = vote(t, x[r]) == y;   correct[t][y] += base
+ *       for every feature f:  xp = x[r] with xp[f] = x[donor(t, f, r)][f];  perm = vote(t, xp) == y
+ *           lost[t][f][y]   += base && !perm
+ *           gained[t][f][y] += !base && perm
+ * Votes and comparisons are exact, so the counts depend on no launch shape and no order of addition,
+ * and a restatement in numpy is equal array by array.  (A feature a row's path does not test cannot
+ * change its vote: only those on the path are re-walked.)
+ * Limits: 1 <= n_rows <= CCDGPU_TRAIN_MAX_ROWS, so that every count is at most 2^27; n_rows == 0
+ * succeeds with all-zero outputs. */
+typedef struct ccdgpu_permutation_params {
+    uint64_t seed;              /* the training request's seed: which rows are out of which bag */
+    uint64_t perm_seed;         /* the seed of the columns' permutations                        */
+} ccdgpu_permutation_params;
+#define CCDGPU_PERM_HASH_C 4294967296ull /* 2^32, the last argument of H for a permutation's key */
+/* The checks a permutation request passes before anything reaches the device (no device needed).
+ * 0, or CCDGPU_EINVAL with the reason in ccdgpu_last_error() ("permutation: ..."), naming the
+ * argument: params or an output NULL; n_rows, n_features or n_classes outside the limits; with
+ * n_rows > 0, x or labels NULL, or a label outside 0 .. n_classes-1 (with its index).  x is not
+ * scanned: the walk defines what a NaN does. */
+int ccdgpu_permutation_check(const double *x, const int32_t *labels, int64_t n_rows, int32_t n_features, int32_t n_classes,
+                             const ccdgpu_permutation_params *params, const int64_t *oob_rows, const int64_t *correct,
+                             const int64_t *lost, const int64_t *gained);
+/* The counts of the rule above: oob_rows and correct [n_trees][n_classes], lost and gained
+ * [n_trees][n_features][n_classes], zeroed by every call.  x is held whole on the device for the call
+ * (CCDGPU_ENOMEM when it does not fit).  Synchronous; *kernel_seconds (may be NULL) gets the device
+ * time of the kernel.  CCDGPU_EINVAL with no forest set, and while a detection begun with
+ * ccdgpu_run_slot_begin is not finished.  The context's forest, the trained forest and the last run
+ * are untouched. */
+int ccdgpu_forest_permutation(ccdgpu_ctx *ctx, const double *x, const int32_t *labels, int64_t n_rows,
+                              const ccdgpu_permutation_params *params, int64_t *oob_rows, int64_t *correct, int64_t *lost,
+                              int64_t *gained, double *kernel_seconds);
+
 /* Prediction of band values from segment models: the modelled surface reflectance of every pixel
  * at dates of the caller's choosing (pyccd's ccd.models.lasso.predict over coefficient_matrix;
  * annual composites, synthetic images, residuals of observations against their model).

@@ -9,7 +9,8 @@ the device over binned features, level by level, by the rule include/ccdgpu.h st
 host), and a forest -- trained or imported, plain arrays either way -- is evaluated on the device
 (ccd_forest.hip through ``ccdgpu.Context.classify`` / ``classify_rows``); there is no CPU path.
 A trained forest is judged by ``oob`` -- every row scored on the device only by the trees whose bag
-it was not in (``Context.forest_oob``), summed up by ``evaluation`` -- and ``feature_importances``.
+it was not in (``Context.forest_oob``), summed up by ``evaluation`` -- by ``feature_importances``, and by
+``permutation_importances``: the out-of-bag votes a shuffled feature loses (``Context.forest_permutation``).
 
 rawPrediction of a row is the sum over the trees, in tree order, of the reached leaf's normalised
 class distribution, indexed by label.  A Spark ``RandomForestClassificationModel`` maps to the
@@ -20,6 +21,7 @@ numbering each tree's nodes in pre-order satisfies the child > parent rule of th
 """
 import collections
 import ctypes
+import math
 
 import numpy as np
 import pyarrow as pa
@@ -36,8 +38,8 @@ class Forest(object):
     right [n_nodes] (feature < 0 marks a leaf), value [n_nodes][n_classes] (leaves' normalised
     class distributions).  A forest trained here (``ccdgpu.Context.train_forest``) also carries
     ``counts`` int64 [n_nodes][n_classes] (the weighted class counts ``value`` is made of), ``seed`` and
-    ``bootstrap``: what ``oob`` and ``feature_importances`` need.  They are None on any other forest,
-    and ``save`` does not keep them."""
+    ``bootstrap``: what ``oob``, ``permutation_importances`` and ``feature_importances`` need.  They are
+    None on any other forest; ``save`` keeps those a forest has."""
 
     counts = seed = bootstrap = None
 
@@ -116,13 +118,28 @@ class Forest(object):
                                int(rf.n_features_in_))
 
     def save(self, path):
-        """Write the arrays as .npz (``path`` as given to numpy.savez: a name gets '.npz')."""
-        np.savez(path, n_features=np.int32(self.n_features), **{k: getattr(self, k) for k in _ARRAYS})
+        """Write the arrays as .npz (``path`` as given to numpy.savez: a name gets '.npz'), with ``seed``,
+        ``bootstrap`` and ``counts`` where the forest has them, so that a trained forest can be judged later."""
+        extra = {}
+        if self.seed is not None:
+            extra['seed'] = np.uint64(self.seed)
+        if self.bootstrap is not None:
+            extra['bootstrap'] = np.bool_(self.bootstrap)
+        if self.counts is not None:
+            extra['counts'] = np.asarray(self.counts, dtype=np.int64)
+        np.savez(path, n_features=np.int32(self.n_features), **extra, **{k: getattr(self, k) for k in _ARRAYS})
 
     @classmethod
     def load(cls, path):
         with np.load(path) as z:
-            return cls.from_arrays(*[z[k] for k in _ARRAYS], n_features=int(z['n_features']))
+            f = cls.from_arrays(*[z[k] for k in _ARRAYS], n_features=int(z['n_features']))
+            if 'seed' in z.files:
+                f.seed = int(z['seed'])
+            if 'bootstrap' in z.files:
+                f.bootstrap = bool(z['bootstrap'])
+            if 'counts' in z.files:
+                f.counts = z['counts'].astype(np.int64)
+            return f
 
 
 def find_splits(matrix, max_bins=32):
@@ -167,7 +184,7 @@ def find_splits(matrix, max_bins=32):
 
 
 def train(dataframe, n_trees=500, max_depth=5, max_bins=32, features_per_node='auto', min_instances_per_node=1,
-          min_info_gain=0.0, bootstrap=True, seed=0, context=None, oob=False):
+          min_info_gain=0.0, bootstrap=True, seed=0, context=None, oob=False, permutation=False, perm_seed=0):
     """Train the forest of the reference's ``train`` (randomforest.py:25-39: 500 trees over
     ``features.dataframe``) on the device and return it as a ``Forest``.  ``dataframe`` is the table of
     ``features.dataframe``: its ``label`` column (trends[0]) the classes, n_classes = max(label) + 1, its
@@ -177,9 +194,13 @@ def train(dataframe, n_trees=500, max_depth=5, max_bins=32, features_per_node='a
     'sqrt', 'all' or a count choose directly.  The bins are ``find_splits(matrix, max_bins)``; the other
     parameters are those of ccdgpu_train_params (include/ccdgpu.h states the rule).  With ``oob`` the
     forest also gets ``forest.oob``: the out-of-bag ``Evaluation`` over the kept rows, in their order
-    (``oob`` below; it needs ``bootstrap`` and leaves the trained forest set as the context's)."""
+    (``oob`` below; it needs ``bootstrap`` and leaves the trained forest set as the context's).  With
+    ``permutation`` it gets ``forest.permutation``: the ``PermutationImportances`` over the kept rows
+    under ``perm_seed`` (``permutation_importances`` below; the same conditions)."""
     if oob and not bootstrap:
         raise ValueError('oob needs bootstrap: without it every bag is every row and no tree is out of bag')
+    if permutation and not bootstrap:
+        raise ValueError('permutation needs bootstrap: without it every bag is every row and no tree is out of bag')
     x = features.matrix(dataframe)
     label = pc.cast(dataframe['label'], pa.float64()).to_numpy(zero_copy_only=False)
     keep = np.isfinite(label) & np.all(np.isfinite(x), axis=1)
@@ -198,6 +219,8 @@ def train(dataframe, n_trees=500, max_depth=5, max_bins=32, features_per_node='a
     forest.rows_trained, forest.rows_dropped = int(x.shape[0]), int(keep.shape[0] - x.shape[0])
     if oob:
         forest.oob = _oob(forest, x, y.astype(np.int32), context=ctx)
+    if permutation:
+        forest.permutation = permutation_importances(forest, x, y.astype(np.int32), perm_seed=perm_seed, context=ctx)
     return forest
 
 
@@ -265,6 +288,81 @@ def oob(forest, x, labels, seed=None, first_row=0, context=None):
 
 
 _oob = oob  # (``train`` has a flag of this name)
+
+
+PermutationImportances = collections.namedtuple(
+    'PermutationImportances', ['importances', 'importances_std', 'class_importances', 'trees_used', 'oob_rows', 'correct',
+                               'lost', 'gained'])
+PermutationImportances.__doc__ = """What ``permutation_importances`` returns: ``importances`` float64 [n_features] (the mean
+over the trees of the share of a tree's out-of-bag rows whose right vote a shuffled column loses, less the
+share it gains: R randomForest's MeanDecreaseAccuracy, unscaled), ``importances_std`` (its sample standard
+deviation over the trees), ``class_importances`` float64 [n_classes][n_features] (the same over the rows
+of one label), ``trees_used`` (the trees with an out-of-bag row), and the integer counts ``oob_rows``,
+``correct`` [n_trees][n_classes], ``lost``, ``gained`` [n_trees][n_features][n_classes] as given."""
+
+
+def permutation_summary(oob_rows, correct, lost, gained):
+    """The ``PermutationImportances`` of the counts of ``Context.forest_permutation`` (host, Python floats
+    over integer sums).  With N_t = sum_k oob_rows[t][k], the trees with N_t == 0 are left out and
+    ``trees_used`` counts the rest; d[t][f] = float(sum_k lost[t][f][k] - sum_k gained[t][f][k]) /
+    float(N_t); importances[f] is the d[t][f] added in tree order, divided by trees_used;
+    importances_std[f] the square root of the sum in tree order of (d[t][f] - importances[f])^2 over
+    trees_used - 1, NaN below two trees.  class_importances[k][f] is the same mean, over the trees with
+    oob_rows[t][k] > 0, of float(lost[t][f][k] - gained[t][f][k]) / float(oob_rows[t][k]); a class no
+    tree saw gets NaN, and without a tree every figure is NaN."""
+    oob_rows, correct = np.asarray(oob_rows, dtype=np.int64), np.asarray(correct, dtype=np.int64)
+    lost, gained = np.asarray(lost, dtype=np.int64), np.asarray(gained, dtype=np.int64)
+    if oob_rows.ndim != 2 or correct.shape != oob_rows.shape or lost.ndim != 3 or gained.shape != lost.shape or \
+            (lost.shape[0], lost.shape[2]) != oob_rows.shape:
+        raise ValueError('oob_rows and correct must be [n_trees][n_classes], lost and gained [n_trees][n_features][n_classes], '
+                         'got %r, %r, %r and %r' % (oob_rows.shape, correct.shape, lost.shape, gained.shape))
+    nt, nf, nc = lost.shape
+    rows, net = oob_rows.tolist(), (lost - gained).tolist()
+    nan = float('nan')
+    used = [t for t in range(nt) if sum(rows[t]) > 0]
+    imp, std = np.full(nf, nan), np.full(nf, nan)
+    per_class = np.full((nc, nf), nan)
+    for f in range(nf):
+        d = [float(sum(net[t][f])) / float(sum(rows[t])) for t in used]
+        if d:
+            total = 0.0
+            for v in d:
+                total += v
+            imp[f] = total / len(d)
+        if len(d) > 1:
+            ss = 0.0
+            for v in d:
+                ss += (v - imp[f]) * (v - imp[f])
+            std[f] = math.sqrt(ss / (len(d) - 1))
+        for k in range(nc):
+            saw = [t for t in used if rows[t][k] > 0]
+            if saw:
+                total = 0.0
+                for t in saw:
+                    total += float(net[t][f][k]) / float(rows[t][k])
+                per_class[k][f] = total / len(saw)
+    return PermutationImportances(imp, std, per_class, len(used), oob_rows, correct, lost, gained)
+
+
+def permutation_importances(forest, x, labels, seed=None, perm_seed=0, context=None):
+    """The out-of-bag permutation importances of ``forest`` over x [n_rows][n_features] and ``labels``
+    [n_rows], the whole training matrix and its labels in training order: for every tree, the rows out
+    of its bag are voted on as they are and with each feature's column shuffled in turn, on the device
+    (include/ccdgpu.h states the rule; ccd_forest.hip through ``ccdgpu.Context.forest_permutation``), and
+    ``permutation_summary`` turns the counts into ``PermutationImportances``.  Unlike
+    ``feature_importances`` this is judged on rows a tree has not seen, and it does not favour the
+    features that offer many split points.  ``seed`` None takes the forest's own; ``perm_seed`` chooses
+    the shuffles.  Sets ``forest`` as the context's forest.  ValueError for a forest trained without
+    bootstrap, or without a seed when none is given."""
+    if forest.bootstrap is not None and not forest.bootstrap:
+        raise ValueError('the forest was trained without bootstrap: every bag is every row and no tree is out of bag')
+    if seed is None:
+        seed = forest.seed
+    if seed is None:
+        raise ValueError('the forest has no seed (it was not trained here): give the seed its bags were drawn with')
+    ctx = _context(context)
+    ctx.set_forest(forest)
+    return permutation_summary(*ctx.forest_permutation(x, labels, seed, perm_seed))
 
 
 def feature_importances(forest):

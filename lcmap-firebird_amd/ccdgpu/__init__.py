@@ -623,7 +623,9 @@ class Context(object):
         self._pending_slot = None  # slot of a run_slot_begin* without its run_slot_end* yet
         self._rows_req = None      # (cx, cy, bufs, width, n_pix, words, cap) of a run_slot_begin_rows
         self._forest_shape = None  # (n_features, n_classes) of the forest set
+        self._forest_trees = 0     # and its tree count
         self.forest_seconds = self.train_seconds = self.predict_seconds = self.products_seconds = self.oob_seconds = 0.0
+        self.permutation_seconds = 0.0
         self.forest_rows = 0
         if copy_cus:
             _check(lib().ccdgpu_init_copy_cus(int(device), int(copy_cus), ctypes.byref(self._ctx)))
@@ -905,11 +907,13 @@ class Context(object):
             raise ValueError(last_error())
         _check(rc)
         self._forest_shape = (int(f.n_features), int(f.n_classes))
+        self._forest_trees = int(f.n_trees)
         self.forest_seconds = 0.0
 
     def clear_forest(self):
         _check(lib().ccdgpu_forest_clear(self._ctx))
         self._forest_shape = None
+        self._forest_trees = 0
 
     def _forest_dims(self):
         """(n_features, n_classes) of the forest set."""
@@ -980,7 +984,7 @@ class Context(object):
         f = Forest(np.empty(nt.value, np.int32), np.empty(nn.value, np.int32), np.empty(nn.value, np.float64),
                    np.empty(nn.value, np.int32), np.empty(nn.value, np.int32), np.empty((nn.value, nc), np.float64), args[3])
         _check(L.ccdgpu_trained_fetch(self._ctx, ctypes.byref(f.struct())))
-        # what the out-of-bag estimate and the importances need (not persisted by Forest.save)
+        # what the out-of-bag estimate and the importances need (Forest.save keeps them)
         f.counts = np.empty((nn.value, nc), np.int64)
         _check(L.ccdgpu_trained_counts(self._ctx, f.counts.ctypes.data, f.counts.size))
         p = keep[-1]
@@ -1006,6 +1010,33 @@ class Context(object):
         _check(rc)
         self.oob_seconds = secs
         return raw, n_oob
+
+    def forest_permutation(self, x, labels, seed, perm_seed=0):
+        """The out-of-bag permutation counts of include/ccdgpu.h (ccdgpu_forest_permutation) of the forest
+        set over x [n_rows][n_features] float64 and labels [n_rows] in 0 .. n_classes-1, the whole
+        training matrix in training order: per tree, over the rows out of its bag under ``seed``,
+        (oob_rows [n_trees][n_classes], correct [n_trees][n_classes], lost and gained
+        [n_trees][n_features][n_classes]), all int64 -- the rows of each label, those the tree votes
+        right, and the right votes lost and gained when a feature's column is shuffled by ``perm_seed``.
+        The kernel seconds are in ``permutation_seconds``.  A request the library refuses raises
+        CcdGpuError with its message."""
+        nf, nc = self._forest_dims()
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if x.ndim != 2 or x.shape[1] != nf:
+            raise ValueError('x must be [n_rows][%d], got %r' % (nf, x.shape))
+        y = np.ascontiguousarray(labels, dtype=np.int32).reshape(-1)
+        if y.shape[0] != x.shape[0]:
+            raise ValueError('labels must be [%d], got %r' % (x.shape[0], y.shape))
+        nt = self._forest_trees
+        p = abi.PermutationParams()
+        p.seed, p.perm_seed = int(seed), int(perm_seed)
+        oob_rows, correct = np.empty((nt, nc), np.int64), np.empty((nt, nc), np.int64)
+        lost, gained = np.empty((nt, nf, nc), np.int64), np.empty((nt, nf, nc), np.int64)
+        rc, secs = _timed(lib().ccdgpu_forest_permutation, self._ctx, x.ctypes.data, y.ctypes.data, x.shape[0], ctypes.byref(p),
+                          oob_rows.ctypes.data, correct.ctypes.data, lost.ctypes.data, gained.ctypes.data)
+        _check(rc)
+        self.permutation_seconds = secs
+        return oob_rows, correct, lost, gained
 
     # prediction of band values from segment models -----------------------------------------------
     def coefficient_matrix(self, dates, avg_days_yr=365.2425):

@@ -22,6 +22,7 @@ TRAIN_MAX_DEPTH = 10       # CCDGPU_TRAIN_MAX_DEPTH
 TRAIN_POISSON = (1580030168, 3160060337, 3950075421, 4213413783, 4279248373, 4292415291, 4294609777,
                  4294923276, 4294962463, 4294966817, 4294967252, 4294967292, 4294967295)
 OOB_CUT = TRAIN_POISSON[0]  # CCDGPU_OOB_CUT: a draw below it is a weight of 0, the row is out of the bag
+PERM_HASH_C = 1 << 32       # CCDGPU_PERM_HASH_C: the last argument of H for a column permutation's key
 ENC_PACK = 1              # CCDGPU_ENC_PACK: flag of ccdgpu_encode_chips_flags / ccdgpu_encoded_bound_flags
 COVER_SPAN, COVER_EXTEND = 0, 1  # CCDGPU_COVER_*: which row a date takes (include/ccdgpu.h)
 PREDICT_F32, PREDICT_I16 = 0, 1  # CCDGPU_PREDICT_*: output type of a prediction
@@ -203,6 +204,11 @@ class OobParams(ctypes.Structure):
     _fields_ = [('seed', ctypes.c_uint64), ('first_row', ctypes.c_int64)]
 
 
+class PermutationParams(ctypes.Structure):
+    """ccdgpu_permutation_params (include/ccdgpu.h)."""
+    _fields_ = [('seed', ctypes.c_uint64), ('perm_seed', ctypes.c_uint64)]
+
+
 def default_train_params():
     p = TrainParams()
     p.n_trees, p.max_depth, p.features_per_node, p.min_instances_per_node = 500, 5, 0, 1
@@ -240,6 +246,7 @@ def _signatures():
     i, i32, i64, u16, dbl, ptr = c.c_int, c.c_int32, c.c_int64, c.c_uint16, c.c_double, c.c_void_p
     ctx, params, secs, n64 = ptr, P(Params), P(dbl), P(i64)   # ccdgpu_ctx *, const ccdgpu_params *, double *, int64_t *
     pparams, products, tparams, oparams = P(ProductParams), P(Products), P(TrainParams), P(OobParams)
+    mparams = P(PermutationParams)
     train = (ptr, ptr, i64, i32, i32, ptr, ptr, tparams)      # x, labels, n_rows, n_features, n_classes, edges, n_edges, params
     rows_into = (ptr, i64, ptr, i64, ptr, i64)                # row_offsets, cap, rows, cap, mask_bits, cap
     encode = (i32, ptr, ptr, ptr, ptr, ptr, i64, i32, u16, u16)
@@ -296,6 +303,8 @@ def _signatures():
         'ccdgpu_oob_check': (i, (ptr, i64, oparams, ptr, ptr)),
         'ccdgpu_forest_oob': (i, (ctx, ptr, i64, oparams, ptr, ptr, secs)),
         'ccdgpu_trained_counts': (i, (ctx, ptr, i64)),
+        'ccdgpu_permutation_check': (i, (ptr, ptr, i64, i32, i32, mparams, ptr, ptr, ptr, ptr)),
+        'ccdgpu_forest_permutation': (i, (ctx, ptr, ptr, i64, mparams, ptr, ptr, ptr, ptr, secs)),
         'ccdgpu_predict_check': (i, (i64, ptr, i64, ptr, i64, ptr, dbl, i32, i32)),
         'ccdgpu_predict': (i, (ctx, i64, ptr, ptr, i64, ptr, dbl, i32, i32, ptr, ptr, secs)),
         'ccdgpu_predict_rows': (i, (ctx, i32, i64, ptr, dbl, i32, i32, ptr, ptr, secs)),

@@ -153,6 +153,14 @@ int ccdk_forest_classify(const CcdForestDev *f, const double *x, const unsigned 
 // (device) = ccd_train_hash_a(seed, t).  out [n_rows][n_classes], n_oob [n_rows] the trees that scored
 int ccdk_forest_oob(const CcdForestDev *f, const double *x, const uint64_t *tree_key, int64_t first_row, int64_t n_rows,
                     float *out, int32_t *n_oob, void *stream);
+// out-of-bag permutation counts (include/ccdgpu.h states the rule) over the whole matrix x
+// [n_rows][n_features] and labels [n_rows] in 0 .. n_classes-1 (device): tree_key as above; perm_ab
+// [n_trees][n_features][2] = the (a, b) of each column's permutation, both below n_rows.  Adds to
+// oob_rows / correct [n_trees][n_classes] and lost / gained [n_trees][n_features][n_classes], which
+// the caller has zeroed
+int ccdk_forest_permutation(const CcdForestDev *f, const double *x, const int32_t *labels, const uint64_t *tree_key,
+                            const uint32_t *perm_ab, int64_t n_rows, uint32_t *oob_rows, uint32_t *correct, uint32_t *lost,
+                            uint32_t *gained, void *stream);
 // feature matrix of a run's rows (ccdgpu_classify_rows): pixel p's rows row_off[p] .. from its
 // segments seg[seg_off[p] ..] (one default row, flagged in skip, without any) and aux[p][5];
 // n_seg / n_rows bound the segment reads and the row writes

@@ -17,7 +17,8 @@
 // leaves' class vectors follow the nodes of their tree, so a chunk carries them too.
 //
 // ccd_forest_oob is the same walk for the out-of-bag estimate: a row takes only the trees whose bag
-// it is not in, by the training rule's hash (ccd_train.h).
+// it is not in, by the training rule's hash (ccd_train.h).  ccd_forest_permutation counts, per tree
+// over the rows out of its bag, the right votes and those lost or gained under a shuffled feature.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -179,6 +180,119 @@ __global__ __launch_bounds__(T) void ccd_forest_oob(CcdForestDev f, const double
     }
 }
 
+static_assert(CCDGPU_FOREST_MAX_FEATURES <= 64, "the features of a path are one bit each of a uint64");
+static_assert(CCDGPU_FOREST_MAX_CLASSES <= W, "lane k of a wave sums the wave's counts of class k");
+
+// One tree for one row, for its vote: walk's descent, with feature sub_f (-1: none) read as sub_v and
+// every tested feature's bit set in `path`; at the leaf the lowest class with the largest value.
+__device__ __forceinline__ int vote(const unsigned char *blob, const double *xs_lane, int xs_stride, int max_depth, int nc,
+                                    int sub_f, double sub_v, uint64_t &path) {
+    const CcdForestNode *nodes = reinterpret_cast<const CcdForestNode *>(blob);
+    CcdForestNode nd = nodes[0];
+    for (int d = 0; d < max_depth && nd.feature >= 0; ++d) {
+        path |= 1ull << nd.feature;
+        const double v = nd.feature == sub_f ? sub_v : xs_lane[nd.feature * xs_stride];
+        nd = nodes[nd.left + (v <= nd.threshold ? 0 : 1)];  // NaN compares false: right
+    }
+    if (nd.feature >= 0) return -1;  // (not reached for a checked forest)
+    const double *val = reinterpret_cast<const double *>(blob) + nd.left;
+    int best = 0;
+    double top = val[0];
+    for (int k = 1; k < nc; ++k) {
+        const double v = val[k];
+        if (v > top) {
+            top = v;
+            best = k;
+        }
+    }
+    return best;
+}
+
+// The out-of-bag permutation counts (include/ccdgpu.h states the rule): ccd_forest_oob's layout and
+// membership test; a row out of a tree's bag takes the tree's vote, which also collects the features
+// its path tests, and then one re-walk per such feature with the donor row's value (an 8-byte gather
+// from x, which is whole in global memory) in its place -- a feature off the path cannot change the
+// vote.  perm_ab [n_trees][n_features] = the (a, b) of each column's permutation, from the host.
+// Counts: oob_rows and correct get an add from every row out of the bag, so a wave sums them first --
+// lane k holds the wave's lanes of label k, two ballots per tree give it the wave's counts of class k
+// -- and adds the non-zero sums, one per class; lost and gained are sparse (an add only where the
+// vote's correctness changed, spread over n_features * n_classes counters per tree: too few per block
+// and counter for an LDS copy to merge them) and go straight to global memory.  The block's feature
+// vectors and the chunk fill the LDS at 33 features, so no counter lives there.  Rows past n_rows
+// neither read, write nor count.
+template <int T>
+__global__ __launch_bounds__(T) void ccd_forest_permutation(CcdForestDev f, const double *__restrict__ x,
+                                                            const int32_t *__restrict__ labels,
+                                                            const uint64_t *__restrict__ tree_key,
+                                                            const uint2 *__restrict__ perm_ab, int64_t n_rows,
+                                                            uint32_t *__restrict__ oob_rows, uint32_t *__restrict__ correct,
+                                                            uint32_t *__restrict__ lost, uint32_t *__restrict__ gained) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    constexpr int XS = T + 1;
+    const int nf = f.n_features, nc = f.n_classes;
+    double *xs = reinterpret_cast<double *>(smem);
+    unsigned char *chunk = smem + feat_bytes(nf, T);
+    const int tid = (int)threadIdx.x, lane = tid % W;
+    const int64_t row0 = (int64_t)blockIdx.x * T;
+    if (row0 >= n_rows) return;
+    const int nrow = n_rows - row0 < T ? (int)(n_rows - row0) : T;
+    const double *xb = x + row0 * nf;
+    for (int i = tid; i < nrow * nf; i += T) {
+        const int r = i / nf, c = i - r * nf;
+        xs[c * XS + r] = xb[i];
+    }
+    const int64_t row = row0 + tid;
+    const bool live = tid < nrow;
+    const uint64_t r = (uint64_t)row, n = (uint64_t)n_rows;
+    const int y = live ? labels[row] : 0;
+    const double inv_n = 1.0 / (double)n_rows;
+    uint64_t of_class = 0;  // in lane k: the wave's live lanes of label k
+    for (int k = 0; k < nc; ++k) {
+        const uint64_t m = __ballot(live && y == k);
+        if (lane == k) of_class = m;
+    }
+    const double *xs_lane = xs + tid;
+    auto one_tree = [&](int t, const unsigned char *blob) {
+        const bool out = live && (uint32_t)(ccd_train_fold(ccd_train_fold(tree_key[t], r), 0) >> 32) < CCDGPU_OOB_CUT;
+        bool base = false;
+        if (out) {
+            uint64_t path = 0, unused = 0;
+            base = vote(blob, xs_lane, XS, f.max_depth, nc, -1, 0.0, path) == y;
+            const uint2 *ab = perm_ab + (int64_t)t * nf;
+            while (path) {
+                const int pf = __ffsll((unsigned long long)path) - 1;
+                path &= path - 1;
+                const uint2 p = ab[pf];
+                const double v = x[ccd_perm_donor(p.x, p.y, r, n, inv_n) * nf + pf];
+                const bool perm = vote(blob, xs_lane, XS, f.max_depth, nc, pf, v, unused) == y;
+                if (perm != base) atomicAdd((base ? lost : gained) + ((int64_t)t * nf + pf) * nc + y, 1u);
+            }
+        }
+        const uint64_t outs = __ballot(out), hits = __ballot(base);
+        if (lane < nc) {
+            const uint32_t n_out = (uint32_t)__popcll(outs & of_class), n_hit = (uint32_t)__popcll(hits & of_class);
+            if (n_out) atomicAdd(oob_rows + (int64_t)t * nc + lane, n_out);
+            if (n_hit) atomicAdd(correct + (int64_t)t * nc + lane, n_hit);
+        }
+    };
+    for (int c = 0; c < f.n_chunks; ++c) {
+        const int t0 = f.chunk_first[c], t1 = f.chunk_first[c + 1];
+        const int64_t base = f.tree_off[t0];
+        const int64_t bytes = f.tree_off[t1] - base;
+        if (bytes <= (int64_t)f.chunk_cap) {
+            __syncthreads();  // the feature vectors are in place / the previous chunk is done with
+            const uint4 *src = reinterpret_cast<const uint4 *>(f.pool + base);
+            uint4 *dst = reinterpret_cast<uint4 *>(chunk);
+            for (int i = tid; i < (int)(bytes >> 4); i += T) dst[i] = src[i];
+            __syncthreads();
+            for (int t = t0; t < t1; ++t) one_tree(t, chunk + (f.tree_off[t] - base));
+        } else {
+            __syncthreads();  // (the feature vectors, when this is the first chunk)
+            for (int t = t0; t < t1; ++t) one_tree(t, f.pool + f.tree_off[t]);
+        }
+    }
+}
+
 // The feature matrix of a run's rows, one wave per pixel, lanes over the elements of its rows:
 // the float32 value the row packer stores (ccd_rows.hip) widened to double, then the pixel's aux
 // values.  n_seg / n_rows bound every read and write.
@@ -259,6 +373,23 @@ int launch_oob_nc(const CcdForestDev &f, const double *x, const uint64_t *tree_k
     return launch_oob<32, T>(f, x, tree_key, first_row, n_rows, out, n_oob, s);
 }
 
+// and for the permutation counts (no accumulators, so no class-count widths)
+template <int T>
+int launch_permutation(const CcdForestDev &f, const double *x, const int32_t *labels, const uint64_t *tree_key,
+                       const uint32_t *perm_ab, int64_t n_rows, uint32_t *oob_rows, uint32_t *correct, uint32_t *lost,
+                       uint32_t *gained, hipStream_t s) {
+    const int lds = feat_bytes(f.n_features, T) + f.chunk_cap;
+    if (lds > LDS_BYTES || f.chunk_cap < 16) return -1;
+    auto k = ccd_forest_permutation<T>;
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
+        return -1;
+    const int64_t blocks = (n_rows + T - 1) / T;
+    if (blocks <= 0 || blocks > 0x7fffffff) return -1;
+    hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(T), lds, s, f, x, labels, tree_key,
+                       reinterpret_cast<const uint2 *>(perm_ab), n_rows, oob_rows, correct, lost, gained);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
 }  // namespace
 
 // Rows per block: 512 where the feature vectors of 512 rows leave a chunk's room in LDS (up to 35
@@ -300,6 +431,21 @@ extern "C" int ccdk_forest_oob(const CcdForestDev *f, const double *x, const uin
         return -1;
     if (f->threads == 512) return launch_oob_nc<512>(*f, x, tree_key, first_row, n_rows, out, n_oob, (hipStream_t)stream);
     if (f->threads == 256) return launch_oob_nc<256>(*f, x, tree_key, first_row, n_rows, out, n_oob, (hipStream_t)stream);
+    return -1;
+}
+
+extern "C" int ccdk_forest_permutation(const CcdForestDev *f, const double *x, const int32_t *labels, const uint64_t *tree_key,
+                                       const uint32_t *perm_ab, int64_t n_rows, uint32_t *oob_rows, uint32_t *correct,
+                                       uint32_t *lost, uint32_t *gained, void *stream) {
+    if (n_rows <= 0) return 0;
+    if (f->n_classes < 1 || f->n_classes > CCDGPU_FOREST_MAX_CLASSES || f->n_features < 1 ||
+        f->n_features > CCDGPU_FOREST_MAX_FEATURES || n_rows > CCDGPU_TRAIN_MAX_ROWS)
+        return -1;
+    hipStream_t s = (hipStream_t)stream;
+    if (f->threads == 512)
+        return launch_permutation<512>(*f, x, labels, tree_key, perm_ab, n_rows, oob_rows, correct, lost, gained, s);
+    if (f->threads == 256)
+        return launch_permutation<256>(*f, x, labels, tree_key, perm_ab, n_rows, oob_rows, correct, lost, gained, s);
     return -1;
 }
 

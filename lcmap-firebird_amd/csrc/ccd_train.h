@@ -45,6 +45,17 @@ CCD_TRAIN_HD uint32_t ccd_train_weight(uint64_t tree_key, uint64_t r, int bootst
     return ccd_train_poisson((uint32_t)(ccd_train_fold(ccd_train_fold(tree_key, r), 0) >> 32));
 }
 
+// The permutation rule's donor (a*r + b) mod n for a, b, r < n <= CCDGPU_TRAIN_MAX_ROWS, inv_n = 1.0 / n:
+// p = a*r + b < n^2, so the quotient is below 2^27 + 1 and its estimate in double (three roundings of
+// 2^-53 each) is off by far less than 1: once truncated it is the quotient or its neighbour, and one
+// step either way gives the exact remainder without a 64-bit division.
+CCD_TRAIN_HD uint64_t ccd_perm_donor(uint32_t a, uint32_t b, uint64_t r, uint64_t n, double inv_n) {
+    const uint64_t p = (uint64_t)a * r + b;
+    const uint64_t q = (uint64_t)((double)p * inv_n);
+    const int64_t rem = (int64_t)(p - q * n);
+    return (uint64_t)(rem < 0 ? rem + (int64_t)n : rem >= (int64_t)n ? rem - (int64_t)n : rem);
+}
+
 // bytes of LDS a histogram block may use for its private counters; a level whose largest tree needs
 // more takes the global path
 #define CCD_TRAIN_LDS_BYTES 49152

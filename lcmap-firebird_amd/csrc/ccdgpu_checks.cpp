@@ -460,6 +460,33 @@ int oob_validate(const double *x, int64_t n_rows, const ccdgpu_oob_params *p, co
     return 0;
 }
 
+int permutation_validate(const double *x, const int32_t *labels, int64_t n_rows, int32_t n_features, int32_t n_classes,
+                         const ccdgpu_permutation_params *p, const int64_t *oob_rows, const int64_t *correct, const int64_t *lost,
+                         const int64_t *gained) {
+    const std::string who = "permutation: ";
+    if (!p) return fail(CCDGPU_EINVAL, who + "params is NULL");
+    if (!oob_rows) return fail(CCDGPU_EINVAL, who + "oob_rows is NULL");
+    if (!correct) return fail(CCDGPU_EINVAL, who + "correct is NULL");
+    if (!lost) return fail(CCDGPU_EINVAL, who + "lost is NULL");
+    if (!gained) return fail(CCDGPU_EINVAL, who + "gained is NULL");
+    if (n_rows < 0 || n_rows > CCDGPU_TRAIN_MAX_ROWS)
+        return fail(CCDGPU_EINVAL, who + "n_rows must be in [0, 2^27], got " + std::to_string(n_rows));
+    if (n_features < 1 || n_features > CCDGPU_FOREST_MAX_FEATURES)
+        return fail(CCDGPU_EINVAL, who + "n_features must be in [1, " + std::to_string(CCDGPU_FOREST_MAX_FEATURES) + "], got " +
+                                       std::to_string(n_features));
+    if (n_classes < 1 || n_classes > CCDGPU_FOREST_MAX_CLASSES)
+        return fail(CCDGPU_EINVAL, who + "n_classes must be in [1, " + std::to_string(CCDGPU_FOREST_MAX_CLASSES) + "], got " +
+                                       std::to_string(n_classes));
+    if (n_rows == 0) return 0;
+    if (!x) return fail(CCDGPU_EINVAL, who + "x is NULL");
+    if (!labels) return fail(CCDGPU_EINVAL, who + "labels is NULL");
+    for (int64_t r = 0; r < n_rows; ++r)
+        if (labels[r] < 0 || labels[r] >= n_classes)
+            return fail(CCDGPU_EINVAL, who + "labels[" + std::to_string(r) + "] = " + std::to_string(labels[r]) +
+                                           " is outside 0 .. " + std::to_string(n_classes - 1));
+    return 0;
+}
+
 }  // namespace ccdhost
 
 using namespace ccdhost;
@@ -544,6 +571,12 @@ int ccdgpu_train_check(const double *x, const int32_t *labels, int64_t n_rows, i
 int ccdgpu_oob_check(const double *x, int64_t n_rows, const ccdgpu_oob_params *params, const float *oob_raw,
                      const int32_t *n_oob) {
     return oob_validate(x, n_rows, params, oob_raw, n_oob);
+}
+
+int ccdgpu_permutation_check(const double *x, const int32_t *labels, int64_t n_rows, int32_t n_features, int32_t n_classes,
+                             const ccdgpu_permutation_params *params, const int64_t *oob_rows, const int64_t *correct,
+                             const int64_t *lost, const int64_t *gained) {
+    return permutation_validate(x, labels, n_rows, n_features, n_classes, params, oob_rows, correct, lost, gained);
 }
 
 int ccdgpu_predict_check(int64_t n_pix, const int64_t *row_offsets, int64_t n_rows, const ccdgpu_row *rows, int64_t n_dates,

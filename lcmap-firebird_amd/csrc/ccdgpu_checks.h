@@ -53,6 +53,10 @@ int train_validate(const double *x, const int32_t *labels, int64_t n_rows, int32
 int32_t train_features_per_node(int32_t n_features, const ccdgpu_train_params *p);
 // The checks of ccdgpu_oob_check.
 int oob_validate(const double *x, int64_t n_rows, const ccdgpu_oob_params *p, const float *oob_raw, const int32_t *n_oob);
+// The checks of ccdgpu_permutation_check.
+int permutation_validate(const double *x, const int32_t *labels, int64_t n_rows, int32_t n_features, int32_t n_classes,
+                         const ccdgpu_permutation_params *p, const int64_t *oob_rows, const int64_t *correct, const int64_t *lost,
+                         const int64_t *gained);
 
 int predict_check_dates(int64_t n_dates, const int64_t *dates, double avg_days_yr);
 int predict_check_modes(int32_t cover, int32_t dtype);

@@ -1,6 +1,7 @@
 // ccdgpu_forest.cpp -- random-forest classification of segment rows (include/ccdgpu.h; kernels in
 // ccd_forest.hip; the forest's checks and its device form in ccdgpu_checks.cpp).
 #include <algorithm>
+#include <numeric>
 
 #include "ccd_train.h"
 #include "ccdgpu_host.h"
@@ -131,6 +132,71 @@ int ccdgpu_forest_oob(ccdgpu_ctx *c, const double *x, int64_t n_rows, const ccdg
         secs += ms * 1e-3;
     }
     if (kernel_seconds) *kernel_seconds = secs;
+    return 0;
+}
+
+int ccdgpu_forest_permutation(ccdgpu_ctx *c, const double *x, const int32_t *labels, int64_t n_rows,
+                              const ccdgpu_permutation_params *p, int64_t *oob_rows, int64_t *correct, int64_t *lost,
+                              int64_t *gained, double *kernel_seconds) {
+    if (kernel_seconds) *kernel_seconds = 0.0;
+    if (!c) return fail(CCDGPU_EINVAL, "NULL ctx");
+    if (!c->has_forest) return fail(CCDGPU_EINVAL, "no forest set (ccdgpu_forest_set)");
+    const int32_t nf = c->forest.n_features, nc = c->forest.n_classes, nt = c->f_n_trees;
+    int rc = busy(c);
+    if (rc || (rc = permutation_validate(x, labels, n_rows, nf, nc, p, oob_rows, correct, lost, gained))) return rc;
+    const size_t dense = (size_t)nt * nc, sparse = dense * nf;
+    std::fill(oob_rows, oob_rows + dense, (int64_t)0);
+    std::fill(correct, correct + dense, (int64_t)0);
+    std::fill(lost, lost + sparse, (int64_t)0);
+    std::fill(gained, gained + sparse, (int64_t)0);
+    if (n_rows == 0) return 0;
+    HIPCHK(hipSetDevice(c->device));
+    // per tree the prefix of the membership hash, per (tree, feature) the column's permutation: the
+    // rule's a (made coprime to n_rows) and b
+    const uint64_t n = (uint64_t)n_rows;
+    std::vector<uint64_t> keys((size_t)nt);
+    std::vector<uint32_t> ab((size_t)nt * nf * 2);
+    for (int32_t t = 0; t < nt; ++t) {
+        keys[t] = ccd_train_hash_a(p->seed, (uint64_t)t);
+        for (int32_t f = 0; f < nf; ++f) {
+            const uint64_t k = ccd_train_hash(p->perm_seed, (uint64_t)t, (uint64_t)f, CCDGPU_PERM_HASH_C);
+            uint64_t a = (k & 0xffffffffull) % n;
+            while (std::gcd(a, n) != 1) a = a + 1 == n ? 0 : a + 1;
+            ab[((size_t)t * nf + f) * 2] = (uint32_t)a;
+            ab[((size_t)t * nf + f) * 2 + 1] = (uint32_t)((k >> 32) % n);
+        }
+    }
+    std::vector<uint32_t> cnt(2 * dense + 2 * sparse);
+    if ((rc = c->f_x.ensure((size_t)(n_rows * nf))) || (rc = c->f_labels.ensure((size_t)n_rows)) ||
+        (rc = c->f_keys.ensure(keys.size())) || (rc = c->f_ab.ensure(ab.size())) || (rc = c->f_cnt.ensure(cnt.size())))
+        return rc;
+    hipStream_t ax = c->aux;
+    // x whole on the device (a row's donors are anywhere in it), uploaded slab by slab
+    for (int64_t r0 = 0; r0 < n_rows; r0 += FOREST_SLAB) {
+        const int64_t m = std::min(FOREST_SLAB, n_rows - r0);
+        HIPCHK(hipMemcpyAsync(c->f_x.p + r0 * nf, x + r0 * nf, sizeof(double) * (size_t)(m * nf), hipMemcpyHostToDevice, ax));
+    }
+    HIPCHK(hipMemcpyAsync(c->f_labels.p, labels, sizeof(int32_t) * (size_t)n_rows, hipMemcpyHostToDevice, ax));
+    HIPCHK(hipMemcpyAsync(c->f_keys.p, keys.data(), sizeof(uint64_t) * keys.size(), hipMemcpyHostToDevice, ax));
+    HIPCHK(hipMemcpyAsync(c->f_ab.p, ab.data(), sizeof(uint32_t) * ab.size(), hipMemcpyHostToDevice, ax));
+    HIPCHK(hipMemsetAsync(c->f_cnt.p, 0, sizeof(uint32_t) * cnt.size(), ax));
+    uint32_t *d_oob = c->f_cnt.p, *d_correct = d_oob + dense, *d_lost = d_correct + dense, *d_gained = d_lost + sparse;
+    HIPCHK(hipEventRecord(c->f_ev[0], ax));
+    if (ccdk_forest_permutation(&c->forest, c->f_x.p, c->f_labels.p, c->f_keys.p, c->f_ab.p, n_rows, d_oob, d_correct, d_lost,
+                                d_gained, ax)) {
+        (void)hipStreamSynchronize(ax);
+        return fail(CCDGPU_EHIP, "forest kernel launch failed");
+    }
+    HIPCHK(hipEventRecord(c->f_ev[1], ax));
+    HIPCHK(hipMemcpyAsync(cnt.data(), c->f_cnt.p, sizeof(uint32_t) * cnt.size(), hipMemcpyDeviceToHost, ax));
+    HIPCHK(hipStreamSynchronize(ax));
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, c->f_ev[0], c->f_ev[1]);
+    if (kernel_seconds) *kernel_seconds = ms * 1e-3;
+    std::copy(cnt.begin(), cnt.begin() + dense, oob_rows);
+    std::copy(cnt.begin() + dense, cnt.begin() + 2 * dense, correct);
+    std::copy(cnt.begin() + 2 * dense, cnt.begin() + 2 * dense + sparse, lost);
+    std::copy(cnt.begin() + 2 * dense + sparse, cnt.end(), gained);
     return 0;
 }
 

@@ -206,6 +206,10 @@ struct ccdgpu_ctx {
     int32_t f_n_trees = 0;
     DevBuf<uint64_t> f_keys;
     DevBuf<int32_t> f_noob;
+    // the permutation counts (ccdgpu_forest_permutation; f_x holds the whole matrix for the call): the
+    // labels, the columns' (a, b) pairs, and the four counter arrays back to back
+    DevBuf<int32_t> f_labels;
+    DevBuf<uint32_t> f_ab, f_cnt;
     // the forest trained last (ccdgpu_forest_train); not the context's forest until it is set
     ccdhost::Trained trained;
     // prediction of band values (ccd_predict.hip): pixels whose output the device holds at a time
