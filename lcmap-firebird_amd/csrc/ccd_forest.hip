@@ -22,6 +22,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/ccdgpu.h"
 #include "ccd_device.h"
 #include "ccd_train.h"
@@ -39,17 +41,99 @@ __host__ __device__ constexpr int feat_bytes(int n_features, int threads) {
     return (n_features * (threads + 1) * 8 + 15) & ~15;
 }
 
-// One tree for one row: at most max_depth branches (the checked forest's depth; a leaf is
-// always reached within it), then the leaf's class vector added to the accumulators.
-template <int NC>
-__device__ __forceinline__ void walk(const unsigned char *blob, const double *xs_lane, int xs_stride, int max_depth, int nc,
-                                     double (&acc)[NC]) {
+// A block's rows, as every walk sees them: the lane's row and its column of the LDS feature vectors,
+// and the chunk room behind them.
+struct BlockRows {
+    const double *xs_lane;  // feature c of the lane's row is xs_lane[c * (T + 1)]
+    unsigned char *chunk;
+    int64_t row;
+    int tid, nrow;  // lanes tid < nrow have a row
+};
+
+// The block frame of the three walks: splits the block's LDS, loads its rows -- row-major in global
+// memory (coalesced) -- transposed into it, and places the lane.  False for a block past n_rows.
+// The rows are in place for every lane only after for_each_chunk's first barrier.
+template <int T>
+__device__ __forceinline__ bool block_rows(const CcdForestDev &f, const double *x, int64_t n_rows, BlockRows &b) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    constexpr int XS = T + 1;
+    const int nf = f.n_features;
+    double *xs = reinterpret_cast<double *>(smem);
+    b.chunk = smem + feat_bytes(nf, T);
+    b.tid = (int)threadIdx.x;
+    const int64_t row0 = (int64_t)blockIdx.x * T;
+    if (row0 >= n_rows) return false;
+    b.nrow = n_rows - row0 < T ? (int)(n_rows - row0) : T;
+    const double *xb = x + row0 * nf;
+    for (int i = b.tid; i < b.nrow * nf; i += T) {
+        const int r = i / nf, c = i - r * nf;
+        xs[c * XS + r] = xb[i];
+    }
+    b.row = row0 + b.tid;
+    b.xs_lane = xs + b.tid;
+    return true;
+}
+
+// The chunk loop of the three walks: the block copies a chunk of whole trees into LDS and hands
+// its trees [t0, t1) to `trees`; a tree larger than a chunk is handed over in global memory.  Tree
+// t's blob is at src + (f.tree_off[t] - first).  Every lane of the block calls this and `trees`
+// runs for every lane (the barriers; the permutation kernel's ballots), so a caller tests its
+// lane's liveness inside `trees`.
+template <int T, class Trees>
+__device__ __forceinline__ void for_each_chunk(const CcdForestDev &f, const BlockRows &b, Trees &&trees) {
+    for (int c = 0; c < f.n_chunks; ++c) {
+        const int t0 = f.chunk_first[c], t1 = f.chunk_first[c + 1];
+        const int64_t base = f.tree_off[t0];
+        const int64_t bytes = f.tree_off[t1] - base;
+        if (bytes <= (int64_t)f.chunk_cap) {
+            __syncthreads();  // the feature vectors are in place / the previous chunk is done with
+            const uint4 *src = reinterpret_cast<const uint4 *>(f.pool + base);
+            uint4 *dst = reinterpret_cast<uint4 *>(b.chunk);
+            for (int i = b.tid; i < (int)(bytes >> 4); i += T) dst[i] = src[i];
+            __syncthreads();
+            trees(t0, t1, static_cast<const unsigned char *>(b.chunk), base);
+        } else {
+            __syncthreads();  // (the feature vectors, when this is the first chunk)
+            trees(t0, t1, f.pool, (int64_t)0);
+        }
+    }
+}
+
+constexpr uint32_t POISSON[CCDGPU_TRAIN_POISSON_N] = CCDGPU_TRAIN_POISSON;
+static_assert(POISSON[0] == CCDGPU_OOB_CUT, "CCDGPU_OOB_CUT is the first entry of CCDGPU_TRAIN_POISSON");
+
+// Row r (its hash index) is out of tree t's bag: the draw u = H(seed, t, r, 0) >> 32 is below P[0],
+// i.e. w(t, r) == 0.  key = tree_key[t] = ccd_train_hash_a(seed, t), the same for every lane (a
+// scalar load per tree); the lane folds r and 0 into it.
+__device__ __forceinline__ bool out_of_bag(uint64_t key, uint64_t r) {
+    return (uint32_t)(ccd_train_fold(ccd_train_fold(key, r), 0) >> 32) < CCDGPU_OOB_CUT;
+}
+
+static_assert(CCDGPU_FOREST_MAX_FEATURES <= 64, "the features of a path are one bit each of a uint64");
+static_assert(CCDGPU_FOREST_MAX_CLASSES <= W, "lane k of a wave sums the wave's counts of class k");
+
+// One tree's descent for one row: at most max_depth branches (the checked forest's depth; a leaf
+// is always reached within it), to the node reached.  SUB (the votes of the permutation counts):
+// feature sub_f (-1: none) is read as sub_v and every tested feature's bit is set in `path`.
+template <bool SUB>
+__device__ __forceinline__ CcdForestNode descend(const unsigned char *blob, const double *xs_lane, int xs_stride, int max_depth,
+                                                 int sub_f, double sub_v, uint64_t &path) {
     const CcdForestNode *nodes = reinterpret_cast<const CcdForestNode *>(blob);
     CcdForestNode nd = nodes[0];
     for (int d = 0; d < max_depth && nd.feature >= 0; ++d) {
-        const double v = xs_lane[nd.feature * xs_stride];
+        if (SUB) path |= 1ull << nd.feature;
+        const double v = SUB && nd.feature == sub_f ? sub_v : xs_lane[nd.feature * xs_stride];
         nd = nodes[nd.left + (v <= nd.threshold ? 0 : 1)];  // NaN compares false: right
     }
+    return nd;
+}
+
+// One tree for one row: the leaf's class vector added to the accumulators.
+template <int NC>
+__device__ __forceinline__ void walk(const unsigned char *blob, const double *xs_lane, int xs_stride, int max_depth, int nc,
+                                     double (&acc)[NC]) {
+    uint64_t unused = 0;
+    const CcdForestNode nd = descend<false>(blob, xs_lane, xs_stride, max_depth, -1, 0.0, unused);
     if (nd.feature >= 0) return;  // (not reached for a checked forest)
     const double *val = reinterpret_cast<const double *>(blob) + nd.left;
 #pragma unroll
@@ -57,143 +141,10 @@ __device__ __forceinline__ void walk(const unsigned char *blob, const double *xs
         if (k < nc) acc[k] += val[k];
 }
 
-template <int NC, int T>
-__global__ __launch_bounds__(T) void ccd_forest_classify(CcdForestDev f, const double *__restrict__ x,
-                                                         const unsigned char *__restrict__ skip, int64_t n_rows,
-                                                         float *__restrict__ out) {
-    extern __shared__ __align__(16) unsigned char smem[];
-    constexpr int XS = T + 1;
-    const int nf = f.n_features, nc = f.n_classes;
-    double *xs = reinterpret_cast<double *>(smem);
-    unsigned char *chunk = smem + feat_bytes(nf, T);
-    const int tid = (int)threadIdx.x;
-    const int64_t row0 = (int64_t)blockIdx.x * T;
-    if (row0 >= n_rows) return;
-    const int nrow = n_rows - row0 < T ? (int)(n_rows - row0) : T;
-    // the block's rows, row-major in global memory (coalesced), transposed into LDS
-    const double *xb = x + row0 * nf;
-    for (int i = tid; i < nrow * nf; i += T) {
-        const int r = i / nf, c = i - r * nf;
-        xs[c * XS + r] = xb[i];
-    }
-    const int64_t row = row0 + tid;
-    const bool live = tid < nrow && !(skip && skip[row]);
-    double acc[NC];
-#pragma unroll
-    for (int k = 0; k < NC; ++k) acc[k] = 0.0;
-    const double *xs_lane = xs + tid;
-    for (int c = 0; c < f.n_chunks; ++c) {
-        const int t0 = f.chunk_first[c], t1 = f.chunk_first[c + 1];
-        const int64_t base = f.tree_off[t0];
-        const int64_t bytes = f.tree_off[t1] - base;
-        if (bytes <= (int64_t)f.chunk_cap) {
-            __syncthreads();  // the feature vectors are in place / the previous chunk is done with
-            const uint4 *src = reinterpret_cast<const uint4 *>(f.pool + base);
-            uint4 *dst = reinterpret_cast<uint4 *>(chunk);
-            for (int i = tid; i < (int)(bytes >> 4); i += T) dst[i] = src[i];
-            __syncthreads();
-            if (live)
-                for (int t = t0; t < t1; ++t) walk<NC>(chunk + (f.tree_off[t] - base), xs_lane, XS, f.max_depth, nc, acc);
-        } else {
-            __syncthreads();  // (the feature vectors, when this is the first chunk)
-            if (live)
-                for (int t = t0; t < t1; ++t) walk<NC>(f.pool + f.tree_off[t], xs_lane, XS, f.max_depth, nc, acc);
-        }
-    }
-    if (tid < nrow) {
-        float *o = out + row * nc;
-#pragma unroll
-        for (int k = 0; k < NC; ++k)
-            if (k < nc) o[k] = live ? __double2float_rn(acc[k]) : __uint_as_float(0x7fc00000u);
-    }
-}
-
-constexpr uint32_t POISSON[CCDGPU_TRAIN_POISSON_N] = CCDGPU_TRAIN_POISSON;
-static_assert(POISSON[0] == CCDGPU_OOB_CUT, "CCDGPU_OOB_CUT is the first entry of CCDGPU_TRAIN_POISSON");
-
-// The out-of-bag walk (include/ccdgpu.h states the rule): ccd_forest_classify's layout -- one lane
-// per row, feature vectors transposed in LDS, the trees streamed through LDS in chunks -- with the
-// rule's membership test in front of every tree.  tree_key[t] = ccd_train_hash_a(seed, t) is the same
-// for every lane (a scalar load per tree); the lane folds its hash index r and 0 into it and walks the
-// tree only when the draw is below CCDGPU_OOB_CUT, i.e. when w(t, r) == 0.  The count of trees that
-// scored the row stays in a register.  Rows past n_rows neither read nor write.
-template <int NC, int T>
-__global__ __launch_bounds__(T) void ccd_forest_oob(CcdForestDev f, const double *__restrict__ x,
-                                                    const uint64_t *__restrict__ tree_key, uint64_t first_row, int64_t n_rows,
-                                                    float *__restrict__ out, int32_t *__restrict__ n_oob) {
-    extern __shared__ __align__(16) unsigned char smem[];
-    constexpr int XS = T + 1;
-    const int nf = f.n_features, nc = f.n_classes;
-    double *xs = reinterpret_cast<double *>(smem);
-    unsigned char *chunk = smem + feat_bytes(nf, T);
-    const int tid = (int)threadIdx.x;
-    const int64_t row0 = (int64_t)blockIdx.x * T;
-    if (row0 >= n_rows) return;
-    const int nrow = n_rows - row0 < T ? (int)(n_rows - row0) : T;
-    const double *xb = x + row0 * nf;
-    for (int i = tid; i < nrow * nf; i += T) {
-        const int r = i / nf, c = i - r * nf;
-        xs[c * XS + r] = xb[i];
-    }
-    const int64_t row = row0 + tid;
-    const bool live = tid < nrow;
-    const uint64_t r = first_row + (uint64_t)row;
-    double acc[NC];
-#pragma unroll
-    for (int k = 0; k < NC; ++k) acc[k] = 0.0;
-    int32_t scored = 0;
-    const double *xs_lane = xs + tid;
-    // out of tree t's bag: the draw u = H(seed, t, r, 0) >> 32 is below P[0]
-    auto out_of_bag = [&](int t) {
-        return live && (uint32_t)(ccd_train_fold(ccd_train_fold(tree_key[t], r), 0) >> 32) < CCDGPU_OOB_CUT;
-    };
-    for (int c = 0; c < f.n_chunks; ++c) {
-        const int t0 = f.chunk_first[c], t1 = f.chunk_first[c + 1];
-        const int64_t base = f.tree_off[t0];
-        const int64_t bytes = f.tree_off[t1] - base;
-        if (bytes <= (int64_t)f.chunk_cap) {
-            __syncthreads();  // the feature vectors are in place / the previous chunk is done with
-            const uint4 *src = reinterpret_cast<const uint4 *>(f.pool + base);
-            uint4 *dst = reinterpret_cast<uint4 *>(chunk);
-            for (int i = tid; i < (int)(bytes >> 4); i += T) dst[i] = src[i];
-            __syncthreads();
-            for (int t = t0; t < t1; ++t)
-                if (out_of_bag(t)) {
-                    walk<NC>(chunk + (f.tree_off[t] - base), xs_lane, XS, f.max_depth, nc, acc);
-                    ++scored;
-                }
-        } else {
-            __syncthreads();  // (the feature vectors, when this is the first chunk)
-            for (int t = t0; t < t1; ++t)
-                if (out_of_bag(t)) {
-                    walk<NC>(f.pool + f.tree_off[t], xs_lane, XS, f.max_depth, nc, acc);
-                    ++scored;
-                }
-        }
-    }
-    if (live) {
-        float *o = out + row * nc;
-#pragma unroll
-        for (int k = 0; k < NC; ++k)
-            if (k < nc) o[k] = __double2float_rn(acc[k]);
-        n_oob[row] = scored;
-    }
-}
-
-static_assert(CCDGPU_FOREST_MAX_FEATURES <= 64, "the features of a path are one bit each of a uint64");
-static_assert(CCDGPU_FOREST_MAX_CLASSES <= W, "lane k of a wave sums the wave's counts of class k");
-
-// One tree for one row, for its vote: walk's descent, with feature sub_f (-1: none) read as sub_v and
-// every tested feature's bit set in `path`; at the leaf the lowest class with the largest value.
+// One tree for one row, for its vote: at the leaf the lowest class with the largest value.
 __device__ __forceinline__ int vote(const unsigned char *blob, const double *xs_lane, int xs_stride, int max_depth, int nc,
                                     int sub_f, double sub_v, uint64_t &path) {
-    const CcdForestNode *nodes = reinterpret_cast<const CcdForestNode *>(blob);
-    CcdForestNode nd = nodes[0];
-    for (int d = 0; d < max_depth && nd.feature >= 0; ++d) {
-        path |= 1ull << nd.feature;
-        const double v = nd.feature == sub_f ? sub_v : xs_lane[nd.feature * xs_stride];
-        nd = nodes[nd.left + (v <= nd.threshold ? 0 : 1)];  // NaN compares false: right
-    }
+    const CcdForestNode nd = descend<true>(blob, xs_lane, xs_stride, max_depth, sub_f, sub_v, path);
     if (nd.feature >= 0) return -1;  // (not reached for a checked forest)
     const double *val = reinterpret_cast<const double *>(blob) + nd.left;
     int best = 0;
@@ -206,6 +157,63 @@ __device__ __forceinline__ int vote(const unsigned char *blob, const double *xs_
         }
     }
     return best;
+}
+
+// The classification: every live row takes every tree; a skipped row's prediction is NaN.
+template <int NC, int T>
+__global__ __launch_bounds__(T) void ccd_forest_classify(CcdForestDev f, const double *__restrict__ x,
+                                                         const unsigned char *__restrict__ skip, int64_t n_rows,
+                                                         float *__restrict__ out) {
+    BlockRows b;
+    if (!block_rows<T>(f, x, n_rows, b)) return;
+    const int nc = f.n_classes;
+    const bool live = b.tid < b.nrow && !(skip && skip[b.row]);
+    double acc[NC];
+#pragma unroll
+    for (int k = 0; k < NC; ++k) acc[k] = 0.0;
+    for_each_chunk<T>(f, b, [&](int t0, int t1, const unsigned char *src, int64_t first) {
+        if (live)
+            for (int t = t0; t < t1; ++t) walk<NC>(src + (f.tree_off[t] - first), b.xs_lane, T + 1, f.max_depth, nc, acc);
+    });
+    if (b.tid < b.nrow) {
+        float *o = out + b.row * nc;
+#pragma unroll
+        for (int k = 0; k < NC; ++k)
+            if (k < nc) o[k] = live ? __double2float_rn(acc[k]) : __uint_as_float(0x7fc00000u);
+    }
+}
+
+// The out-of-bag walk (include/ccdgpu.h states the rule): ccd_forest_classify's layout -- one lane
+// per row, feature vectors transposed in LDS, the trees streamed through LDS in chunks -- with the
+// rule's membership test in front of every tree: the lane walks the tree only when out_of_bag.  The
+// count of trees that scored the row stays in a register.  Rows past n_rows neither read nor write.
+template <int NC, int T>
+__global__ __launch_bounds__(T) void ccd_forest_oob(CcdForestDev f, const double *__restrict__ x,
+                                                    const uint64_t *__restrict__ tree_key, uint64_t first_row, int64_t n_rows,
+                                                    float *__restrict__ out, int32_t *__restrict__ n_oob) {
+    BlockRows b;
+    if (!block_rows<T>(f, x, n_rows, b)) return;
+    const int nc = f.n_classes;
+    const bool live = b.tid < b.nrow;
+    const uint64_t r = first_row + (uint64_t)b.row;
+    double acc[NC];
+#pragma unroll
+    for (int k = 0; k < NC; ++k) acc[k] = 0.0;
+    int32_t scored = 0;
+    for_each_chunk<T>(f, b, [&](int t0, int t1, const unsigned char *src, int64_t first) {
+        for (int t = t0; t < t1; ++t)
+            if (live && out_of_bag(tree_key[t], r)) {
+                walk<NC>(src + (f.tree_off[t] - first), b.xs_lane, T + 1, f.max_depth, nc, acc);
+                ++scored;
+            }
+    });
+    if (live) {
+        float *o = out + b.row * nc;
+#pragma unroll
+        for (int k = 0; k < NC; ++k)
+            if (k < nc) o[k] = __double2float_rn(acc[k]);
+        n_oob[b.row] = scored;
+    }
 }
 
 // The out-of-bag permutation counts (include/ccdgpu.h states the rule): ccd_forest_oob's layout and
@@ -227,44 +235,32 @@ __global__ __launch_bounds__(T) void ccd_forest_permutation(CcdForestDev f, cons
                                                             const uint2 *__restrict__ perm_ab, int64_t n_rows,
                                                             uint32_t *__restrict__ oob_rows, uint32_t *__restrict__ correct,
                                                             uint32_t *__restrict__ lost, uint32_t *__restrict__ gained) {
-    extern __shared__ __align__(16) unsigned char smem[];
-    constexpr int XS = T + 1;
-    const int nf = f.n_features, nc = f.n_classes;
-    double *xs = reinterpret_cast<double *>(smem);
-    unsigned char *chunk = smem + feat_bytes(nf, T);
-    const int tid = (int)threadIdx.x, lane = tid % W;
-    const int64_t row0 = (int64_t)blockIdx.x * T;
-    if (row0 >= n_rows) return;
-    const int nrow = n_rows - row0 < T ? (int)(n_rows - row0) : T;
-    const double *xb = x + row0 * nf;
-    for (int i = tid; i < nrow * nf; i += T) {
-        const int r = i / nf, c = i - r * nf;
-        xs[c * XS + r] = xb[i];
-    }
-    const int64_t row = row0 + tid;
-    const bool live = tid < nrow;
-    const uint64_t r = (uint64_t)row, n = (uint64_t)n_rows;
-    const int y = live ? labels[row] : 0;
+    BlockRows b;
+    if (!block_rows<T>(f, x, n_rows, b)) return;
+    const int nf = f.n_features, nc = f.n_classes, lane = b.tid % W;
+    const bool live = b.tid < b.nrow;
+    const uint64_t r = (uint64_t)b.row, n = (uint64_t)n_rows;
+    const int y = live ? labels[b.row] : 0;
     const double inv_n = 1.0 / (double)n_rows;
     uint64_t of_class = 0;  // in lane k: the wave's live lanes of label k
     for (int k = 0; k < nc; ++k) {
         const uint64_t m = __ballot(live && y == k);
         if (lane == k) of_class = m;
     }
-    const double *xs_lane = xs + tid;
+    // every lane of the wave runs this (the ballots); `live` and `out` are tested inside
     auto one_tree = [&](int t, const unsigned char *blob) {
-        const bool out = live && (uint32_t)(ccd_train_fold(ccd_train_fold(tree_key[t], r), 0) >> 32) < CCDGPU_OOB_CUT;
+        const bool out = live && out_of_bag(tree_key[t], r);
         bool base = false;
         if (out) {
             uint64_t path = 0, unused = 0;
-            base = vote(blob, xs_lane, XS, f.max_depth, nc, -1, 0.0, path) == y;
+            base = vote(blob, b.xs_lane, T + 1, f.max_depth, nc, -1, 0.0, path) == y;
             const uint2 *ab = perm_ab + (int64_t)t * nf;
             while (path) {
                 const int pf = __ffsll((unsigned long long)path) - 1;
                 path &= path - 1;
                 const uint2 p = ab[pf];
                 const double v = x[ccd_perm_donor(p.x, p.y, r, n, inv_n) * nf + pf];
-                const bool perm = vote(blob, xs_lane, XS, f.max_depth, nc, pf, v, unused) == y;
+                const bool perm = vote(blob, b.xs_lane, T + 1, f.max_depth, nc, pf, v, unused) == y;
                 if (perm != base) atomicAdd((base ? lost : gained) + ((int64_t)t * nf + pf) * nc + y, 1u);
             }
         }
@@ -275,22 +271,9 @@ __global__ __launch_bounds__(T) void ccd_forest_permutation(CcdForestDev f, cons
             if (n_hit) atomicAdd(correct + (int64_t)t * nc + lane, n_hit);
         }
     };
-    for (int c = 0; c < f.n_chunks; ++c) {
-        const int t0 = f.chunk_first[c], t1 = f.chunk_first[c + 1];
-        const int64_t base = f.tree_off[t0];
-        const int64_t bytes = f.tree_off[t1] - base;
-        if (bytes <= (int64_t)f.chunk_cap) {
-            __syncthreads();  // the feature vectors are in place / the previous chunk is done with
-            const uint4 *src = reinterpret_cast<const uint4 *>(f.pool + base);
-            uint4 *dst = reinterpret_cast<uint4 *>(chunk);
-            for (int i = tid; i < (int)(bytes >> 4); i += T) dst[i] = src[i];
-            __syncthreads();
-            for (int t = t0; t < t1; ++t) one_tree(t, chunk + (f.tree_off[t] - base));
-        } else {
-            __syncthreads();  // (the feature vectors, when this is the first chunk)
-            for (int t = t0; t < t1; ++t) one_tree(t, f.pool + f.tree_off[t]);
-        }
-    }
+    for_each_chunk<T>(f, b, [&](int t0, int t1, const unsigned char *src, int64_t first) {
+        for (int t = t0; t < t1; ++t) one_tree(t, src + (f.tree_off[t] - first));
+    });
 }
 
 // The feature matrix of a run's rows, one wave per pixel, lanes over the elements of its rows:
@@ -324,70 +307,47 @@ __global__ __launch_bounds__(256) void ccd_forest_gather(const ccdgpu_segment *_
     }
 }
 
-template <int NC, int T>
-int launch(const CcdForestDev &f, const double *x, const unsigned char *skip, int64_t n_rows, float *out, hipStream_t s) {
+// The launch of a walk: one block of T lanes per T rows, the feature vectors and a chunk in its LDS.
+template <int T, class... P, class... A>
+int launch(void (*k)(P...), const CcdForestDev &f, int64_t n_rows, hipStream_t s, A... args) {
     const int lds = feat_bytes(f.n_features, T) + f.chunk_cap;
     if (lds > LDS_BYTES || f.chunk_cap < 16) return -1;
-    auto k = ccd_forest_classify<NC, T>;
     if (hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
         return -1;
     const int64_t blocks = (n_rows + T - 1) / T;
     if (blocks <= 0 || blocks > 0x7fffffff) return -1;
-    hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(T), lds, s, f, x, skip, n_rows, out);
+    hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(T), lds, s, f, args...);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-template <int T>
-int launch_nc(const CcdForestDev &f, const double *x, const unsigned char *skip, int64_t n_rows, float *out, hipStream_t s) {
-    const int nc = f.n_classes;
-    if (nc <= 2) return launch<2, T>(f, x, skip, n_rows, out, s);
-    if (nc <= 4) return launch<4, T>(f, x, skip, n_rows, out, s);
-    if (nc <= 9) return launch<9, T>(f, x, skip, n_rows, out, s);
-    if (nc <= 16) return launch<16, T>(f, x, skip, n_rows, out, s);
-    return launch<32, T>(f, x, skip, n_rows, out, s);
+template <int N>
+using Int = std::integral_constant<int, N>;
+
+// go(Int<T>) for the forest's rows per block
+template <class Go>
+int with_threads(const CcdForestDev &f, Go &&go) {
+    if (f.threads == 512) return go(Int<512>{});
+    if (f.threads == 256) return go(Int<256>{});
+    return -1;
 }
 
-// the same launch shape for the out-of-bag walk
-template <int NC, int T>
-int launch_oob(const CcdForestDev &f, const double *x, const uint64_t *tree_key, int64_t first_row, int64_t n_rows, float *out,
-               int32_t *n_oob, hipStream_t s) {
-    const int lds = feat_bytes(f.n_features, T) + f.chunk_cap;
-    if (lds > LDS_BYTES || f.chunk_cap < 16) return -1;
-    auto k = ccd_forest_oob<NC, T>;
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
-        return -1;
-    const int64_t blocks = (n_rows + T - 1) / T;
-    if (blocks <= 0 || blocks > 0x7fffffff) return -1;
-    hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(T), lds, s, f, x, tree_key, (uint64_t)first_row, n_rows, out, n_oob);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+// go(Int<NC>, Int<T>) for the accumulators' width -- the least of 2, 4, 9, 16, 32 that holds the
+// forest's classes -- and its rows per block
+template <class Go>
+int with_width(const CcdForestDev &f, Go &&go) {
+    return with_threads(f, [&](auto t) {
+        const int nc = f.n_classes;
+        if (nc <= 2) return go(Int<2>{}, t);
+        if (nc <= 4) return go(Int<4>{}, t);
+        if (nc <= 9) return go(Int<9>{}, t);
+        if (nc <= 16) return go(Int<16>{}, t);
+        return go(Int<32>{}, t);
+    });
 }
 
-template <int T>
-int launch_oob_nc(const CcdForestDev &f, const double *x, const uint64_t *tree_key, int64_t first_row, int64_t n_rows,
-                  float *out, int32_t *n_oob, hipStream_t s) {
-    const int nc = f.n_classes;
-    if (nc <= 2) return launch_oob<2, T>(f, x, tree_key, first_row, n_rows, out, n_oob, s);
-    if (nc <= 4) return launch_oob<4, T>(f, x, tree_key, first_row, n_rows, out, n_oob, s);
-    if (nc <= 9) return launch_oob<9, T>(f, x, tree_key, first_row, n_rows, out, n_oob, s);
-    if (nc <= 16) return launch_oob<16, T>(f, x, tree_key, first_row, n_rows, out, n_oob, s);
-    return launch_oob<32, T>(f, x, tree_key, first_row, n_rows, out, n_oob, s);
-}
-
-// and for the permutation counts (no accumulators, so no class-count widths)
-template <int T>
-int launch_permutation(const CcdForestDev &f, const double *x, const int32_t *labels, const uint64_t *tree_key,
-                       const uint32_t *perm_ab, int64_t n_rows, uint32_t *oob_rows, uint32_t *correct, uint32_t *lost,
-                       uint32_t *gained, hipStream_t s) {
-    const int lds = feat_bytes(f.n_features, T) + f.chunk_cap;
-    if (lds > LDS_BYTES || f.chunk_cap < 16) return -1;
-    auto k = ccd_forest_permutation<T>;
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
-        return -1;
-    const int64_t blocks = (n_rows + T - 1) / T;
-    if (blocks <= 0 || blocks > 0x7fffffff) return -1;
-    hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(T), lds, s, f, x, labels, tree_key,
-                       reinterpret_cast<const uint2 *>(perm_ab), n_rows, oob_rows, correct, lost, gained);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+bool dims_ok(const CcdForestDev &f) {
+    return f.n_classes >= 1 && f.n_classes <= CCDGPU_FOREST_MAX_CLASSES && f.n_features >= 1 &&
+           f.n_features <= CCDGPU_FOREST_MAX_FEATURES;
 }
 
 }  // namespace
@@ -415,38 +375,35 @@ extern "C" int32_t ccdk_forest_chunk_cap(int32_t n_features) {
 extern "C" int ccdk_forest_classify(const CcdForestDev *f, const double *x, const unsigned char *skip, int64_t n_rows,
                                     float *out, void *stream) {
     if (n_rows <= 0) return 0;
-    if (f->n_classes < 1 || f->n_classes > CCDGPU_FOREST_MAX_CLASSES || f->n_features < 1 ||
-        f->n_features > CCDGPU_FOREST_MAX_FEATURES)
-        return -1;
-    if (f->threads == 512) return launch_nc<512>(*f, x, skip, n_rows, out, (hipStream_t)stream);
-    if (f->threads == 256) return launch_nc<256>(*f, x, skip, n_rows, out, (hipStream_t)stream);
-    return -1;
+    if (!dims_ok(*f)) return -1;
+    return with_width(*f, [&](auto nc, auto t) {
+        constexpr int NC = decltype(nc)::value, T = decltype(t)::value;
+        return launch<T>(ccd_forest_classify<NC, T>, *f, n_rows, (hipStream_t)stream, x, skip, n_rows, out);
+    });
 }
 
 extern "C" int ccdk_forest_oob(const CcdForestDev *f, const double *x, const uint64_t *tree_key, int64_t first_row,
                                int64_t n_rows, float *out, int32_t *n_oob, void *stream) {
     if (n_rows <= 0) return 0;
-    if (f->n_classes < 1 || f->n_classes > CCDGPU_FOREST_MAX_CLASSES || f->n_features < 1 ||
-        f->n_features > CCDGPU_FOREST_MAX_FEATURES || first_row < 0)
-        return -1;
-    if (f->threads == 512) return launch_oob_nc<512>(*f, x, tree_key, first_row, n_rows, out, n_oob, (hipStream_t)stream);
-    if (f->threads == 256) return launch_oob_nc<256>(*f, x, tree_key, first_row, n_rows, out, n_oob, (hipStream_t)stream);
-    return -1;
+    if (!dims_ok(*f) || first_row < 0) return -1;
+    return with_width(*f, [&](auto nc, auto t) {
+        constexpr int NC = decltype(nc)::value, T = decltype(t)::value;
+        return launch<T>(ccd_forest_oob<NC, T>, *f, n_rows, (hipStream_t)stream, x, tree_key, (uint64_t)first_row, n_rows, out,
+                         n_oob);
+    });
 }
 
+// (no accumulators, so no class-count widths)
 extern "C" int ccdk_forest_permutation(const CcdForestDev *f, const double *x, const int32_t *labels, const uint64_t *tree_key,
                                        const uint32_t *perm_ab, int64_t n_rows, uint32_t *oob_rows, uint32_t *correct,
                                        uint32_t *lost, uint32_t *gained, void *stream) {
     if (n_rows <= 0) return 0;
-    if (f->n_classes < 1 || f->n_classes > CCDGPU_FOREST_MAX_CLASSES || f->n_features < 1 ||
-        f->n_features > CCDGPU_FOREST_MAX_FEATURES || n_rows > CCDGPU_TRAIN_MAX_ROWS)
-        return -1;
-    hipStream_t s = (hipStream_t)stream;
-    if (f->threads == 512)
-        return launch_permutation<512>(*f, x, labels, tree_key, perm_ab, n_rows, oob_rows, correct, lost, gained, s);
-    if (f->threads == 256)
-        return launch_permutation<256>(*f, x, labels, tree_key, perm_ab, n_rows, oob_rows, correct, lost, gained, s);
-    return -1;
+    if (!dims_ok(*f) || n_rows > CCDGPU_TRAIN_MAX_ROWS) return -1;
+    return with_threads(*f, [&](auto t) {
+        constexpr int T = decltype(t)::value;
+        return launch<T>(ccd_forest_permutation<T>, *f, n_rows, (hipStream_t)stream, x, labels, tree_key,
+                         reinterpret_cast<const uint2 *>(perm_ab), n_rows, oob_rows, correct, lost, gained);
+    });
 }
 
 extern "C" int ccdk_forest_gather(const ccdgpu_segment *seg, const int64_t *seg_off, const int64_t *row_off,

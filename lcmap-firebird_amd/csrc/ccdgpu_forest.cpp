@@ -12,6 +12,69 @@ using namespace ccdhost;
 // a row's result does not depend on its slab)
 static const int64_t FOREST_SLAB = (int64_t)1 << 20;
 
+// What every call that walks the context's forest checks first.
+static int enter(ccdgpu_ctx *c, double *kernel_seconds) {
+    if (kernel_seconds) *kernel_seconds = 0.0;
+    if (!c) return fail(CCDGPU_EINVAL, "NULL ctx");
+    if (!c->has_forest) return fail(CCDGPU_EINVAL, "no forest set (ccdgpu_forest_set)");
+    return busy(c);
+}
+
+// The timed part of a call: `launch` enqueues its kernels (non-zero: one did not launch) between the two forest events.
+template <class Launch>
+static int timed(ccdgpu_ctx *c, Launch &&launch) {
+    hipStream_t ax = c->aux;
+    HIPCHK(hipEventRecord(c->f_ev[0], ax));
+    if (launch()) {
+        (void)hipStreamSynchronize(ax);
+        return fail(CCDGPU_EHIP, "forest kernel launch failed");
+    }
+    HIPCHK(hipEventRecord(c->f_ev[1], ax));
+    return 0;
+}
+
+// The end of what was enqueued behind timed(): the seconds between its events, added to *secs.
+static int finish(ccdgpu_ctx *c, double *secs) {
+    HIPCHK(hipStreamSynchronize(c->aux));
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, c->f_ev[0], c->f_ev[1]);
+    if (secs) *secs += ms * 1e-3;
+    return 0;
+}
+
+// The host-matrix path: x goes through f_x in slabs; launch(r0, n) enqueues the kernel of rows [r0, r0 + n), which
+// leaves their predictions in f_out (to raw).  The out-of-bag walk's: keys go up first, f_noob's counts come down too.
+template <class Launch>
+static int by_slab(ccdgpu_ctx *c, const double *x, int64_t n_rows, float *raw, const std::vector<uint64_t> *keys,
+                   int32_t *n_oob, double *kernel_seconds, Launch &&launch) {
+    const int64_t nf = c->forest.n_features, nc = c->forest.n_classes;
+    const int64_t slab = std::min(n_rows, FOREST_SLAB);
+    int rc = c->f_x.ensure((size_t)(slab * nf));
+    if (rc || (rc = c->f_out.ensure((size_t)(slab * nc))) || (n_oob && (rc = c->f_noob.ensure((size_t)slab))) ||
+        (keys && (rc = c->f_keys.ensure(keys->size()))))
+        return rc;
+    hipStream_t ax = c->aux;
+    if (keys) HIPCHK(hipMemcpyAsync(c->f_keys.p, keys->data(), sizeof(uint64_t) * keys->size(), hipMemcpyHostToDevice, ax));
+    double secs = 0.0;
+    for (int64_t r0 = 0; r0 < n_rows; r0 += slab) {
+        const int64_t n = std::min(slab, n_rows - r0);
+        HIPCHK(hipMemcpyAsync(c->f_x.p, x + r0 * nf, sizeof(double) * (size_t)(n * nf), hipMemcpyHostToDevice, ax));
+        if ((rc = timed(c, [&] { return launch(r0, n); }))) return rc;
+        HIPCHK(hipMemcpyAsync(raw + r0 * nc, c->f_out.p, sizeof(float) * (size_t)(n * nc), hipMemcpyDeviceToHost, ax));
+        if (n_oob) HIPCHK(hipMemcpyAsync(n_oob + r0, c->f_noob.p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, ax));
+        if ((rc = finish(c, &secs))) return rc;
+    }
+    if (kernel_seconds) *kernel_seconds = secs;
+    return 0;
+}
+
+// the per-tree prefix of the membership hash, once per call
+static std::vector<uint64_t> tree_keys(const ccdgpu_ctx *c, uint64_t seed) {
+    std::vector<uint64_t> keys((size_t)c->f_n_trees);
+    for (int32_t t = 0; t < c->f_n_trees; ++t) keys[t] = ccd_train_hash_a(seed, (uint64_t)t);
+    return keys;
+}
+
 extern "C" {
 
 int ccdgpu_forest_clear(ccdgpu_ctx *c) {
@@ -62,88 +125,36 @@ int ccdgpu_forest_set(ccdgpu_ctx *c, const ccdgpu_forest *f) {
 }
 
 int ccdgpu_classify(ccdgpu_ctx *c, const double *features, int64_t n_rows, float *rfrawp, double *kernel_seconds) {
-    if (kernel_seconds) *kernel_seconds = 0.0;
-    if (!c) return fail(CCDGPU_EINVAL, "NULL ctx");
-    if (!c->has_forest) return fail(CCDGPU_EINVAL, "no forest set (ccdgpu_forest_set)");
-    int rc = busy(c);
+    int rc = enter(c, kernel_seconds);
     if (rc) return rc;
     if (n_rows < 0) return fail(CCDGPU_EINVAL, "n_rows must be >= 0");
     if (n_rows == 0) return 0;
     if (!features || !rfrawp) return fail(CCDGPU_EINVAL, "NULL argument");
     HIPCHK(hipSetDevice(c->device));
-    const int64_t nf = c->forest.n_features, nc = c->forest.n_classes;
-    const int64_t slab = std::min(n_rows, FOREST_SLAB);
-    if ((rc = c->f_x.ensure((size_t)(slab * nf))) || (rc = c->f_out.ensure((size_t)(slab * nc)))) return rc;
-    hipStream_t ax = c->aux;
-    double secs = 0.0;
-    for (int64_t r0 = 0; r0 < n_rows; r0 += slab) {
-        const int64_t n = std::min(slab, n_rows - r0);
-        HIPCHK(hipMemcpyAsync(c->f_x.p, features + r0 * nf, sizeof(double) * (size_t)(n * nf), hipMemcpyHostToDevice, ax));
-        HIPCHK(hipEventRecord(c->f_ev[0], ax));
-        if (ccdk_forest_classify(&c->forest, c->f_x.p, nullptr, n, c->f_out.p, ax)) {
-            (void)hipStreamSynchronize(ax);
-            return fail(CCDGPU_EHIP, "forest kernel launch failed");
-        }
-        HIPCHK(hipEventRecord(c->f_ev[1], ax));
-        HIPCHK(hipMemcpyAsync(rfrawp + r0 * nc, c->f_out.p, sizeof(float) * (size_t)(n * nc), hipMemcpyDeviceToHost, ax));
-        HIPCHK(hipStreamSynchronize(ax));
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, c->f_ev[0], c->f_ev[1]);
-        secs += ms * 1e-3;
-    }
-    if (kernel_seconds) *kernel_seconds = secs;
-    return 0;
+    return by_slab(c, features, n_rows, rfrawp, nullptr, nullptr, kernel_seconds, [&](int64_t, int64_t n) {
+        return ccdk_forest_classify(&c->forest, c->f_x.p, nullptr, n, c->f_out.p, c->aux);
+    });
 }
 
 int ccdgpu_forest_oob(ccdgpu_ctx *c, const double *x, int64_t n_rows, const ccdgpu_oob_params *p, float *oob_raw, int32_t *n_oob,
                       double *kernel_seconds) {
-    if (kernel_seconds) *kernel_seconds = 0.0;
-    if (!c) return fail(CCDGPU_EINVAL, "NULL ctx");
-    if (!c->has_forest) return fail(CCDGPU_EINVAL, "no forest set (ccdgpu_forest_set)");
-    int rc = busy(c);
+    int rc = enter(c, kernel_seconds);
     if (rc || (rc = oob_validate(x, n_rows, p, oob_raw, n_oob))) return rc;
     if (n_rows == 0) return 0;
     HIPCHK(hipSetDevice(c->device));
-    const int64_t nf = c->forest.n_features, nc = c->forest.n_classes;
-    const int64_t slab = std::min(n_rows, FOREST_SLAB);
-    // the per-tree prefix of the rule's hash, once per call
-    std::vector<uint64_t> keys((size_t)c->f_n_trees);
-    for (int32_t t = 0; t < c->f_n_trees; ++t) keys[t] = ccd_train_hash_a(p->seed, (uint64_t)t);
-    if ((rc = c->f_x.ensure((size_t)(slab * nf))) || (rc = c->f_out.ensure((size_t)(slab * nc))) ||
-        (rc = c->f_noob.ensure((size_t)slab)) || (rc = c->f_keys.ensure(keys.size())))
-        return rc;
-    hipStream_t ax = c->aux;
-    HIPCHK(hipMemcpyAsync(c->f_keys.p, keys.data(), sizeof(uint64_t) * keys.size(), hipMemcpyHostToDevice, ax));
-    double secs = 0.0;
-    for (int64_t r0 = 0; r0 < n_rows; r0 += slab) {
-        const int64_t n = std::min(slab, n_rows - r0);
-        HIPCHK(hipMemcpyAsync(c->f_x.p, x + r0 * nf, sizeof(double) * (size_t)(n * nf), hipMemcpyHostToDevice, ax));
-        HIPCHK(hipEventRecord(c->f_ev[0], ax));
-        if (ccdk_forest_oob(&c->forest, c->f_x.p, c->f_keys.p, p->first_row + r0, n, c->f_out.p, c->f_noob.p, ax)) {
-            (void)hipStreamSynchronize(ax);
-            return fail(CCDGPU_EHIP, "forest kernel launch failed");
-        }
-        HIPCHK(hipEventRecord(c->f_ev[1], ax));
-        HIPCHK(hipMemcpyAsync(oob_raw + r0 * nc, c->f_out.p, sizeof(float) * (size_t)(n * nc), hipMemcpyDeviceToHost, ax));
-        HIPCHK(hipMemcpyAsync(n_oob + r0, c->f_noob.p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, ax));
-        HIPCHK(hipStreamSynchronize(ax));
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, c->f_ev[0], c->f_ev[1]);
-        secs += ms * 1e-3;
-    }
-    if (kernel_seconds) *kernel_seconds = secs;
-    return 0;
+    const std::vector<uint64_t> keys = tree_keys(c, p->seed);
+    return by_slab(c, x, n_rows, oob_raw, &keys, n_oob, kernel_seconds, [&](int64_t r0, int64_t n) {
+        return ccdk_forest_oob(&c->forest, c->f_x.p, c->f_keys.p, p->first_row + r0, n, c->f_out.p, c->f_noob.p, c->aux);
+    });
 }
 
 int ccdgpu_forest_permutation(ccdgpu_ctx *c, const double *x, const int32_t *labels, int64_t n_rows,
                               const ccdgpu_permutation_params *p, int64_t *oob_rows, int64_t *correct, int64_t *lost,
                               int64_t *gained, double *kernel_seconds) {
-    if (kernel_seconds) *kernel_seconds = 0.0;
-    if (!c) return fail(CCDGPU_EINVAL, "NULL ctx");
-    if (!c->has_forest) return fail(CCDGPU_EINVAL, "no forest set (ccdgpu_forest_set)");
+    int rc = enter(c, kernel_seconds);
+    if (rc) return rc;
     const int32_t nf = c->forest.n_features, nc = c->forest.n_classes, nt = c->f_n_trees;
-    int rc = busy(c);
-    if (rc || (rc = permutation_validate(x, labels, n_rows, nf, nc, p, oob_rows, correct, lost, gained))) return rc;
+    if ((rc = permutation_validate(x, labels, n_rows, nf, nc, p, oob_rows, correct, lost, gained))) return rc;
     const size_t dense = (size_t)nt * nc, sparse = dense * nf;
     std::fill(oob_rows, oob_rows + dense, (int64_t)0);
     std::fill(correct, correct + dense, (int64_t)0);
@@ -151,13 +162,11 @@ int ccdgpu_forest_permutation(ccdgpu_ctx *c, const double *x, const int32_t *lab
     std::fill(gained, gained + sparse, (int64_t)0);
     if (n_rows == 0) return 0;
     HIPCHK(hipSetDevice(c->device));
-    // per tree the prefix of the membership hash, per (tree, feature) the column's permutation: the
-    // rule's a (made coprime to n_rows) and b
+    // per (tree, feature) the column's permutation: the rule's a (made coprime to n_rows) and b
     const uint64_t n = (uint64_t)n_rows;
-    std::vector<uint64_t> keys((size_t)nt);
+    const std::vector<uint64_t> keys = tree_keys(c, p->seed);
     std::vector<uint32_t> ab((size_t)nt * nf * 2);
-    for (int32_t t = 0; t < nt; ++t) {
-        keys[t] = ccd_train_hash_a(p->seed, (uint64_t)t);
+    for (int32_t t = 0; t < nt; ++t)
         for (int32_t f = 0; f < nf; ++f) {
             const uint64_t k = ccd_train_hash(p->perm_seed, (uint64_t)t, (uint64_t)f, CCDGPU_PERM_HASH_C);
             uint64_t a = (k & 0xffffffffull) % n;
@@ -165,7 +174,6 @@ int ccdgpu_forest_permutation(ccdgpu_ctx *c, const double *x, const int32_t *lab
             ab[((size_t)t * nf + f) * 2] = (uint32_t)a;
             ab[((size_t)t * nf + f) * 2 + 1] = (uint32_t)((k >> 32) % n);
         }
-    }
     std::vector<uint32_t> cnt(2 * dense + 2 * sparse);
     if ((rc = c->f_x.ensure((size_t)(n_rows * nf))) || (rc = c->f_labels.ensure((size_t)n_rows)) ||
         (rc = c->f_keys.ensure(keys.size())) || (rc = c->f_ab.ensure(ab.size())) || (rc = c->f_cnt.ensure(cnt.size())))
@@ -181,18 +189,13 @@ int ccdgpu_forest_permutation(ccdgpu_ctx *c, const double *x, const int32_t *lab
     HIPCHK(hipMemcpyAsync(c->f_ab.p, ab.data(), sizeof(uint32_t) * ab.size(), hipMemcpyHostToDevice, ax));
     HIPCHK(hipMemsetAsync(c->f_cnt.p, 0, sizeof(uint32_t) * cnt.size(), ax));
     uint32_t *d_oob = c->f_cnt.p, *d_correct = d_oob + dense, *d_lost = d_correct + dense, *d_gained = d_lost + sparse;
-    HIPCHK(hipEventRecord(c->f_ev[0], ax));
-    if (ccdk_forest_permutation(&c->forest, c->f_x.p, c->f_labels.p, c->f_keys.p, c->f_ab.p, n_rows, d_oob, d_correct, d_lost,
-                                d_gained, ax)) {
-        (void)hipStreamSynchronize(ax);
-        return fail(CCDGPU_EHIP, "forest kernel launch failed");
-    }
-    HIPCHK(hipEventRecord(c->f_ev[1], ax));
+    if ((rc = timed(c, [&] {
+             return ccdk_forest_permutation(&c->forest, c->f_x.p, c->f_labels.p, c->f_keys.p, c->f_ab.p, n_rows, d_oob, d_correct,
+                                            d_lost, d_gained, ax);
+         })))
+        return rc;
     HIPCHK(hipMemcpyAsync(cnt.data(), c->f_cnt.p, sizeof(uint32_t) * cnt.size(), hipMemcpyDeviceToHost, ax));
-    HIPCHK(hipStreamSynchronize(ax));
-    float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, c->f_ev[0], c->f_ev[1]);
-    if (kernel_seconds) *kernel_seconds = ms * 1e-3;
+    if ((rc = finish(c, kernel_seconds))) return rc;
     std::copy(cnt.begin(), cnt.begin() + dense, oob_rows);
     std::copy(cnt.begin() + dense, cnt.begin() + 2 * dense, correct);
     std::copy(cnt.begin() + 2 * dense, cnt.begin() + 2 * dense + sparse, lost);
@@ -230,19 +233,14 @@ int ccdgpu_classify_rows(ccdgpu_ctx *c, const double *aux, float *rfrawp, int64_
         return rc;
     hipStream_t ax = c->aux;
     HIPCHK(hipMemcpyAsync(c->f_aux.p, aux, sizeof(double) * (size_t)np * 5, hipMemcpyHostToDevice, ax));
-    HIPCHK(hipEventRecord(c->f_ev[0], ax));
-    if (ccdk_forest_gather(c->csr.p + s0, c->seg_off1.p, c->row_off.p, c->f_aux.p, np, n_seg, nr, c->f_x.p, c->f_skip.p, ax) ||
-        ccdk_forest_classify(&c->forest, c->f_x.p, c->f_skip.p, nr, c->f_out.p, ax)) {
-        (void)hipStreamSynchronize(ax);
-        return fail(CCDGPU_EHIP, "forest kernel launch failed");
-    }
-    HIPCHK(hipEventRecord(c->f_ev[1], ax));
+    if ((rc = timed(c, [&] {
+             return ccdk_forest_gather(c->csr.p + s0, c->seg_off1.p, c->row_off.p, c->f_aux.p, np, n_seg, nr, c->f_x.p,
+                                       c->f_skip.p, ax) ||
+                    ccdk_forest_classify(&c->forest, c->f_x.p, c->f_skip.p, nr, c->f_out.p, ax);
+         })))
+        return rc;
     HIPCHK(hipMemcpyAsync(rfrawp, c->f_out.p, sizeof(float) * (size_t)(nr * nc), hipMemcpyDeviceToHost, ax));
-    HIPCHK(hipStreamSynchronize(ax));
-    float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, c->f_ev[0], c->f_ev[1]);
-    if (kernel_seconds) *kernel_seconds = ms * 1e-3;
-    return 0;
+    return finish(c, kernel_seconds);
 }
 
 }  // extern "C"

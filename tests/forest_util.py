@@ -50,6 +50,15 @@ class Arrays(object):
         return [getattr(self, k) for k in ARRAYS] + [self.n_features]
 
 
+def concatenated(parts):
+    """The forests ``parts`` (same features and classes) as one: their trees in order, child indices shifted."""
+    base = np.cumsum([0] + [p.feature.shape[0] for p in parts[:-1]])
+    cat = lambda k: np.concatenate([getattr(p, k) for p in parts])
+    shift = lambda k: np.concatenate([np.where(getattr(p, k) >= 0, getattr(p, k) + b, -1) for p, b in zip(parts, base)])
+    root = np.concatenate([p.root + b for p, b in zip(parts, base)])
+    return Arrays(root, cat('feature'), cat('threshold'), shift('left'), shift('right'), cat('value'), parts[0].n_features)
+
+
 def random_forest(seed, n_trees, max_depth, n_features, n_classes, p_leaf=0.15, rows=None):
     """Seeded forest, nodes in pre-order (child > parent).  A node above max_depth becomes a leaf
     with probability p_leaf (p_leaf=0: complete trees; max_depth=0: single-leaf trees).  Leaf

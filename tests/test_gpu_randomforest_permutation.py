@@ -100,6 +100,27 @@ def test_a_tree_walked_from_global_memory(ctx):
     assert got[2][1].any() and got[3][1].any()  # the big tree's votes change
 
 
+def test_one_forest_three_walks(ctx):
+    """The classification, the out-of-bag walk and the permutation counts share one chunk loop: one forest
+    whose trees need several LDS chunks on either side of a tree that no chunk holds, over 513 rows (a
+    second block of one row), through all three against their restatements."""
+    nf, nc, n = 5, 3, 513
+    cap = ccdgpu.lib().ccdk_forest_chunk_cap(nf)
+    small, big = 63 * 16 + 32 * nc * 8, 1023 * 16 + 512 * nc * 8  # the blobs of complete trees of depth 5 and 9
+    assert ccdgpu.lib().ccdk_forest_threads(nf) == 512 and big > cap and 14 * small > cap
+    f = forest_util.concatenated([forest_util.random_forest(61, 14, 5, nf, nc, p_leaf=0.0),
+                                  forest_util.random_forest(62, 1, 9, nf, nc, p_leaf=0.0),
+                                  forest_util.random_forest(63, 14, 5, nf, nc, p_leaf=0.0)])
+    assert f.root.shape[0] == 29 and f.feature.shape[0] == 28 * 63 + 1023
+    x, y = _rows(64, n, nf), _labels(64, n, nc)
+    got = _same(ctx, f, x, y, seed=9, perm_seed=2)
+    assert got[2][14].any() and got[3][14].any() and got[2][28].any()  # the big tree and the last chunk count
+    assert np.array_equal(ctx.classify(x), forest_util.walk(f, x))
+    raw, scored = ctx.forest_oob(x, 9)
+    ref_raw, ref_scored = oob_util.oob(f, x, 9)
+    assert np.array_equal(raw, ref_raw) and np.array_equal(scored, ref_scored)
+
+
 def test_a_stump_on_the_last_of_64_features(ctx):
     """Bit 63 of the path mask.  A row's label is its side of the stump, so every vote is right; shuffling
     column 63 loses exactly the out-of-bag rows whose donor sits on the other side."""
