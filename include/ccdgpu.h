@@ -493,6 +493,51 @@ int ccdgpu_forest_train(ccdgpu_ctx *ctx, const double *x, const int32_t *labels,
 int ccdgpu_trained_size(ccdgpu_ctx *ctx, int32_t *n_trees, int32_t *n_nodes);
 int ccdgpu_trained_fetch(ccdgpu_ctx *ctx, ccdgpu_forest *into);
 
+/* The bin edges of training, found on the device: Spark ML's rule for continuous features
+ * (RandomForest.findSplitsForContinuousFeature with every row a sample), which
+ * ccdc.randomforest.find_splits computes on the host with a sort per column.  The rule is restated
+ * here over positions of the sorted column, the form the device computes; the two are equal array by
+ * array, so no tolerance is involved.
+ *
+ * Inputs.  x [n_rows][n_features] double, all finite; max_bins.  Limits: n_rows 0 ..
+ * CCDGPU_TRAIN_MAX_ROWS (0 rows: no launch, no edges), n_features 1 .. CCDGPU_FOREST_MAX_FEATURES,
+ * max_bins 2 .. CCDGPU_TRAIN_MAX_EDGES + 1.
+ *
+ * Per feature, over the column's n = n_rows values:
+ * Key.  v + 0.0, so that -0.0 and +0.0 are one value.
+ * Sorted column.  s[0 .. n-1] is the column in ascending order.
+ * Boundary.  A position p in 1 .. n-1 with s[p] != s[p-1].  The boundaries in order are p_1 < p_2 <
+ *     .. < p_B, and p_{B+1} = n.  The column has D = B + 1 distinct values.
+ * Midpoint of boundary p_i: (s[p_i - 1] + s[p_i]) / 2.0, two IEEE double operations in that order, no
+ *     contraction.  An overflow to +-inf is kept (ccdgpu_train_check refuses such an edge later).
+ * Few distinct values.  If D - 1 <= max_bins - 1, every boundary's midpoint is a candidate, in order.
+ * Many distinct values.  Otherwise stride = (double)n / (double)max_bins and target = stride; for i =
+ *     1, 2, .. B in order: if fabs((double)p_i - target) < fabs((double)p_{i+1} - target), the midpoint
+ *     of boundary i is a candidate and target += stride.  (p_i is the number of values below the i-th
+ *     distinct value, the running count of the host rule, so no counts are needed.  Rounding of a
+ *     subtraction is monotone, so a boundary with p_{i+1} <= target is never taken and the walk may
+ *     search for the first one whose successor is above the target.  At most max_bins - 1 are taken.)
+ * Deduplication.  A candidate that is not above the candidate before it (neighbouring doubles,
+ *     repeated inf) is dropped; the rest, in order, are the feature's edges: strictly increasing, at most
+ *     CCDGPU_TRAIN_MAX_EDGES.
+ * The result is a pure function of x and max_bins: it does not depend on the order of the rows, on
+ * launch shapes or on how the features are grouped. */
+/* The checks of a request (no device needed).  0, or CCDGPU_EINVAL with the reason in
+ * ccdgpu_last_error(), naming the argument, and for a non-finite value its row and feature: a count
+ * outside the limits above; with n_rows > 0, a NULL x or a non-finite x. */
+int ccdgpu_splits_check(const double *x, int64_t n_rows, int32_t n_features, int32_t max_bins);
+/* Check and find the edges: edges [n_features][CCDGPU_TRAIN_MAX_EDGES] gets feature f's edges at
+ * edges[f][0 .. n_edges[f]) and zeros behind them, n_edges [n_features] their counts (what
+ * ccdgpu_forest_train takes once packed back to back).  Synchronous; *kernel_seconds (may be NULL)
+ * gets the device time of the kernels.  x goes up in the slabs training uses; the features are sorted
+ * in groups whose two key buffers (16 bytes per row and feature) stay within 2 GiB, a single feature's
+ * where n_rows alone exceeds that (CCDGPU_SPLITS_GROUP_FEATURES in the environment, a test knob, fixes
+ * the group size); the result does not depend on the grouping.  The context's forest and the trained
+ * forest are untouched.  Refused with CCDGPU_EINVAL while a detection begun with
+ * ccdgpu_run_slot_begin is not finished. */
+int ccdgpu_forest_find_splits(ccdgpu_ctx *ctx, const double *x, int64_t n_rows, int32_t n_features, int32_t max_bins,
+                              double *edges, int32_t *n_edges, double *kernel_seconds);
+
 /* Out-of-bag evaluation of a forest: every row scored only by the trees whose bag it is not in.
  * The bags are not stored: w(t,r) of the training rule above is a function of (seed, t, r), so
  * "row r is out of tree t's bag" is recomputed wherever it is needed.

@@ -5,8 +5,9 @@ The reference trains a Spark ML RandomForestClassifier (500 trees, randomforest.
 ``features.dataframe`` and keeps the model's ``rawPrediction`` per segment as ``rfrawp``
 (array<float>; ``segment.join`` puts it on the segment rows).  Here ``train`` grows the forest on
 the device over binned features, level by level, by the rule include/ccdgpu.h states
-(ccd_train.hip through ``ccdgpu.Context.train_forest``; ``find_splits`` chooses the bins on the
-host), and a forest -- trained or imported, plain arrays either way -- is evaluated on the device
+(ccd_train.hip through ``ccdgpu.Context.train_forest``; ``find_splits`` chooses the bins, on the
+host or, given a context, on the device: ccd_splits.hip), and a forest -- trained or imported, plain
+arrays either way -- is evaluated on the device
 (ccd_forest.hip through ``ccdgpu.Context.classify`` / ``classify_rows``); there is no CPU path.
 A trained forest is judged by ``oob`` -- every row scored on the device only by the trees whose bag
 it was not in (``Context.forest_oob``), summed up by ``evaluation`` -- by ``feature_importances``, and by
@@ -142,7 +143,7 @@ class Forest(object):
             return f
 
 
-def find_splits(matrix, max_bins=32):
+def find_splits(matrix, max_bins=32, context=None):
     """Bin edges of the columns of ``matrix`` [n_rows][n_features] (finite values): a list of
     increasing float64 arrays, one per feature -- Spark ML's rule for continuous features
     (RandomForest.findSplitsForContinuousFeature, with every row a sample).
@@ -154,7 +155,15 @@ def find_splits(matrix, max_bins=32):
     count n_0 + .. + n_{i-1}, for i = 1, 2, .. in order: if |c - target| < |c + n_i - target| the
     midpoint (d_{i-1} + d_i) / 2 is an edge and target grows by stride; then c grows by n_i.  A
     midpoint equal to the edge before it (neighbouring doubles) is dropped, so the edges strictly
-    increase.  2 <= max_bins <= 64 (the device's bin matrix is uint8 with at most 63 edges)."""
+    increase.  2 <= max_bins <= 64 (the device's bin matrix is uint8 with at most 63 edges).
+
+    Without a ``context`` the edges are computed here on the host (a sort per column).  With a
+    ``ccdgpu.Context`` they are found on the device (``Context.find_splits``: ccd_splits.hip, the same
+    rule over positions of the sorted columns) and are equal to the host's array by array."""
+    if context is not None:
+        if np.ndim(matrix) != 2:
+            raise ValueError('matrix must be [n_rows][n_features], got %r' % (np.shape(matrix),))
+        return context.find_splits(matrix, max_bins)
     x = np.asarray(matrix, dtype=np.float64)
     if x.ndim != 2:
         raise ValueError('matrix must be [n_rows][n_features], got %r' % (x.shape,))
@@ -184,19 +193,24 @@ def find_splits(matrix, max_bins=32):
 
 
 def train(dataframe, n_trees=500, max_depth=5, max_bins=32, features_per_node='auto', min_instances_per_node=1,
-          min_info_gain=0.0, bootstrap=True, seed=0, context=None, oob=False, permutation=False, perm_seed=0):
+          min_info_gain=0.0, bootstrap=True, seed=0, context=None, oob=False, permutation=False, perm_seed=0,
+          splits='host'):
     """Train the forest of the reference's ``train`` (randomforest.py:25-39: 500 trees over
     ``features.dataframe``) on the device and return it as a ``Forest``.  ``dataframe`` is the table of
     ``features.dataframe``: its ``label`` column (trends[0]) the classes, n_classes = max(label) + 1, its
     ``features`` column the 33 features.  Rows with a null label or a non-finite feature are dropped;
     the forest's ``rows_dropped`` / ``rows_trained`` say how many went and stayed.  features_per_node
     'auto' is every feature for one tree and 'sqrt' otherwise, as Spark's ``featureSubsetStrategy``;
-    'sqrt', 'all' or a count choose directly.  The bins are ``find_splits(matrix, max_bins)``; the other
+    'sqrt', 'all' or a count choose directly.  The bins are ``find_splits(matrix, max_bins)``, computed on
+    the host with ``splits`` 'host' and on the context the forest is trained on with 'device' (the same
+    edges either way); the other
     parameters are those of ccdgpu_train_params (include/ccdgpu.h states the rule).  With ``oob`` the
     forest also gets ``forest.oob``: the out-of-bag ``Evaluation`` over the kept rows, in their order
     (``oob`` below; it needs ``bootstrap`` and leaves the trained forest set as the context's).  With
     ``permutation`` it gets ``forest.permutation``: the ``PermutationImportances`` over the kept rows
     under ``perm_seed`` (``permutation_importances`` below; the same conditions)."""
+    if splits not in ('host', 'device'):
+        raise ValueError("splits must be 'host' or 'device', got %r" % (splits,))
     if oob and not bootstrap:
         raise ValueError('oob needs bootstrap: without it every bag is every row and no tree is out of bag')
     if permutation and not bootstrap:
@@ -212,8 +226,9 @@ def train(dataframe, n_trees=500, max_depth=5, max_bins=32, features_per_node='a
     if features_per_node == 'auto':
         features_per_node = 'all' if int(n_trees) == 1 else 'sqrt'
     ctx = _context(context)
+    edges = find_splits(x, max_bins, context=ctx if splits == 'device' else None)
     forest = ctx.train_forest(
-        x, y.astype(np.int32), find_splits(x, max_bins), n_trees=n_trees, max_depth=max_depth,
+        x, y.astype(np.int32), edges, n_trees=n_trees, max_depth=max_depth,
         features_per_node=features_per_node, min_instances_per_node=min_instances_per_node, min_info_gain=min_info_gain,
         bootstrap=bool(bootstrap), seed=seed)
     forest.rows_trained, forest.rows_dropped = int(x.shape[0]), int(keep.shape[0] - x.shape[0])

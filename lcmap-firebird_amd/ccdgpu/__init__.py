@@ -571,6 +571,23 @@ def train_check(x, labels, edges, n_classes=None, **params):
         raise ValueError(last_error())
 
 
+def _splits_args(x, max_bins):
+    """The arguments of ccdgpu_splits_check / ccdgpu_forest_find_splits between the context and the
+    outputs, from x [n_rows][n_features]; returns (arguments, the array they point into)."""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    if x.ndim != 2:
+        raise ValueError('x must be [n_rows][n_features], got %r' % (x.shape,))
+    return (x.ctypes.data, x.shape[0], x.shape[1], int(max_bins)), x
+
+
+def splits_check(x, max_bins=32):
+    """ccdgpu_splits_check (no device needed) over an array-like, as ``Context.find_splits`` takes it.
+    Raises ValueError with the library's message."""
+    args, keep = _splits_args(x, max_bins)  # (keep: alive over the call)
+    if lib().ccdgpu_splits_check(*args) != 0:
+        raise ValueError(last_error())
+
+
 class _Staged(object):
     """The shape of a staged batch, one record for every staging form: the host arrays to keep
     alive, the chips' pixel and observation counts, and whether the batch is a ChipBatch (an
@@ -625,7 +642,7 @@ class Context(object):
         self._forest_shape = None  # (n_features, n_classes) of the forest set
         self._forest_trees = 0     # and its tree count
         self.forest_seconds = self.train_seconds = self.predict_seconds = self.products_seconds = self.oob_seconds = 0.0
-        self.permutation_seconds = 0.0
+        self.permutation_seconds = self.splits_seconds = 0.0
         self.forest_rows = 0
         if copy_cus:
             _check(lib().ccdgpu_init_copy_cus(int(device), int(copy_cus), ctypes.byref(self._ctx)))
@@ -990,6 +1007,24 @@ class Context(object):
         p = keep[-1]
         f.seed, f.bootstrap = int(p.seed), bool(p.bootstrap)
         return f
+
+    def find_splits(self, x, max_bins=32):
+        """The bin edges of x [n_rows][n_features] float64 (finite values), found on the device by the
+        position form of the rule in include/ccdgpu.h (ccdgpu_forest_find_splits): a list of increasing
+        float64 arrays, one per feature, equal array by array to ``ccdc.randomforest.find_splits`` on the
+        host.  The kernel seconds are in ``splits_seconds``.  A request the library's checks refuse (a
+        non-finite value, max_bins outside 2 .. 64: ccdgpu_splits_check, run by the call before anything
+        is launched) raises ValueError with the library's message; any other refusal raises CcdGpuError."""
+        args, keep = _splits_args(x, max_bins)  # (keep: alive over the call)
+        nf = args[2]
+        edges = np.empty((nf, abi.TRAIN_MAX_EDGES), dtype=np.float64)
+        n_edges = np.empty(nf, dtype=np.int32)
+        rc, secs = _timed(lib().ccdgpu_forest_find_splits, self._ctx, *(args + (edges.ctypes.data, n_edges.ctypes.data)))
+        if rc == abi.E_INVAL and last_error().startswith('splits: '):
+            raise ValueError(last_error())
+        _check(rc)
+        self.splits_seconds = secs
+        return [np.ascontiguousarray(edges[f, :n_edges[f]]) for f in range(nf)]
 
     def forest_oob(self, x, seed, first_row=0):
         """The out-of-bag walk of include/ccdgpu.h (ccdgpu_forest_oob) of x [n_rows][n_features] float64

@@ -300,6 +300,8 @@ def _signatures():
         'ccdgpu_forest_train': (i, (ctx,) + train + (secs,)),
         'ccdgpu_trained_size': (i, (ctx, P(i32), P(i32))),
         'ccdgpu_trained_fetch': (i, (ctx, P(Forest))),
+        'ccdgpu_splits_check': (i, (ptr, i64, i32, i32)),
+        'ccdgpu_forest_find_splits': (i, (ctx, ptr, i64, i32, i32, ptr, ptr, secs)),
         'ccdgpu_oob_check': (i, (ptr, i64, oparams, ptr, ptr)),
         'ccdgpu_forest_oob': (i, (ctx, ptr, i64, oparams, ptr, ptr, secs)),
         'ccdgpu_trained_counts': (i, (ctx, ptr, i64)),

@@ -445,6 +445,25 @@ int32_t train_features_per_node(int32_t n_features, const ccdgpu_train_params *p
     return m < n_features ? m : n_features;
 }
 
+int splits_validate(const double *x, int64_t n_rows, int32_t n_features, int32_t max_bins) {
+    const std::string who = "splits: ";
+    if (n_rows < 0 || n_rows > CCDGPU_TRAIN_MAX_ROWS)
+        return fail(CCDGPU_EINVAL, who + "n_rows must be in [0, 2^27], got " + std::to_string(n_rows));
+    if (n_features < 1 || n_features > CCDGPU_FOREST_MAX_FEATURES)
+        return fail(CCDGPU_EINVAL, who + "n_features must be in [1, " + std::to_string(CCDGPU_FOREST_MAX_FEATURES) + "], got " +
+                                       std::to_string(n_features));
+    if (max_bins < 2 || max_bins > CCDGPU_TRAIN_MAX_EDGES + 1)
+        return fail(CCDGPU_EINVAL, who + "max_bins must be in [2, " + std::to_string(CCDGPU_TRAIN_MAX_EDGES + 1) + "], got " +
+                                       std::to_string(max_bins));
+    if (n_rows == 0) return 0;
+    if (!x) return fail(CCDGPU_EINVAL, who + "x is NULL");
+    for (int64_t i = 0, n = n_rows * n_features; i < n; ++i)
+        if (!std::isfinite(x[i]))
+            return fail(CCDGPU_EINVAL, who + "x[" + std::to_string(i / n_features) + "][" + std::to_string(i % n_features) +
+                                           "] is not finite");
+    return 0;
+}
+
 int oob_validate(const double *x, int64_t n_rows, const ccdgpu_oob_params *p, const float *oob_raw, const int32_t *n_oob) {
     const std::string who = "oob: ";
     if (!p) return fail(CCDGPU_EINVAL, who + "params is NULL");
@@ -566,6 +585,10 @@ void ccdgpu_train_params_default(ccdgpu_train_params *p) {
 int ccdgpu_train_check(const double *x, const int32_t *labels, int64_t n_rows, int32_t n_features, int32_t n_classes,
                        const double *edges, const int32_t *n_edges, const ccdgpu_train_params *params) {
     return train_validate(x, labels, n_rows, n_features, n_classes, edges, n_edges, params);
+}
+
+int ccdgpu_splits_check(const double *x, int64_t n_rows, int32_t n_features, int32_t max_bins) {
+    return splits_validate(x, n_rows, n_features, max_bins);
 }
 
 int ccdgpu_oob_check(const double *x, int64_t n_rows, const ccdgpu_oob_params *params, const float *oob_raw,

@@ -51,6 +51,8 @@ int forest_build(const ccdgpu_forest *f, int32_t cap, std::vector<unsigned char>
 int train_validate(const double *x, const int32_t *labels, int64_t n_rows, int32_t n_features, int32_t n_classes,
                    const double *edges, const int32_t *n_edges, const ccdgpu_train_params *p);
 int32_t train_features_per_node(int32_t n_features, const ccdgpu_train_params *p);
+// The checks of ccdgpu_splits_check.
+int splits_validate(const double *x, int64_t n_rows, int32_t n_features, int32_t max_bins);
 // The checks of ccdgpu_oob_check.
 int oob_validate(const double *x, int64_t n_rows, const ccdgpu_oob_params *p, const float *oob_raw, const int32_t *n_oob);
 // The checks of ccdgpu_permutation_check.

@@ -1,5 +1,5 @@
 // ccdgpu_host.h -- what the host API's units share (ccdgpu_api.cpp: contexts, staging, detection,
-// row chain and fetches; ccdgpu_forest.cpp; ccdgpu_train.cpp; ccdgpu_predict.cpp; ccdgpu_products.cpp): the owners of device memory,
+// row chain and fetches; ccdgpu_forest.cpp; ccdgpu_train.cpp; ccdgpu_splits.cpp; ccdgpu_predict.cpp; ccdgpu_products.cpp): the owners of device memory,
 // pinned memory and events, and the context.  Private to csrc/.
 #pragma once
 #include <hip/hip_runtime.h>
